@@ -6,8 +6,14 @@ batch) over 512 synthetic random Connect4 boards already resident in HBM:
     fused with the policy/value heads (az_linear_heads_fwd).
 Weights are random-init (PCG64) with the reference's shapes (no checkpoint download).
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]
+    python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N     (one rank/GPU)
+
+A plain run sets up, warms up, times the K steps and prints the result line; --dump-outputs
+DIR also writes the last step's log pi / pi / v as DIR/<name>.npy (same arguments, same
+inputs: seeded boards and weights).  --full adds every other leg to the line: the guard that
+the step is bit-identical to the unfused calls, rooflines, the CNN / batch-1 / large-batch /
+config-5 / self-play / training legs and the CPU baselines.
 
 Each rank evaluates its own batch (rows are independent, no collective on the data path):
 value = N * B * K / max-over-ranks(time).  Rank 0 prints ONE JSON line.
@@ -45,6 +51,13 @@ def parse():
                     help="untimed full steps before the warmup until this much wall time has "
                          "passed (GPU clock ramp); 0 = none")
     ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (log pi, pi, v "
+                         "of this rank's batch) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the bit-identity guard, the rooflines, the CNN / "
+                         "batch-1 / large-batch / config-5 / self-play / training legs and the "
+                         "CPU baselines (every option below only matters with --full)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="bounded CPU-baseline sample (rank 0, N=1 only)")
     ap.add_argument("--no-cpu", action="store_true")
@@ -900,6 +913,41 @@ def _leaf_timeouts():
     return wrappers.leaf_timeouts()
 
 
+def headline(args, world, B, elapsed, settle_ms, settle_steps):
+    """The result line of a plain run (--full adds the other legs to it)."""
+    value = world * B * args.steps / elapsed
+    return {
+        "metric": METRIC, "value": round(value, 1), "unit": "board evals/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "clock_settle": {"ms": round(settle_ms, 1), "steps": settle_steps,
+                         "note": "untimed full steps before the warmup (GPU clock ramp)"},
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (fp16x2 row-scaled split, 3 products: output_transform GEMMs and the "
+                 "trunk's conv2 split each fp32 operand row, power-of-two scaled, into 2 fp16 "
+                 "terms, 3 fp16 MFMA products, fp32 accumulate; ~22-bit operands: "
+                 "tests/test_gpu_trained.py holds pi / v / log pi to 1e-5 of float64 and of "
+                 "the reference on its trained weights, margins reported)",
+        "data": "synthetic (uniform random {-1,0,1} 7x7 boards; PCG64 random-init weights "
+                "of the reference shapes)",
+        "config": {"workload": "Connect4 (reference 7x7+pass board) Connect4GNN "
+                               "predict_with_gnn per-board fwd: trunk -> output_transform "
+                               "-> heads, batch of random boards per GPU",
+                   "global_batch": B * world, "batch_per_gpu": B, "feature_dim": F,
+                   "parallelism": f"dp{world} (independent shards, no collective)"},
+        "full": bool(args.full),
+    }
+
+
+def dump_outputs(d, tensors, rank, world):
+    """--dump-outputs: what the last timed step returned to its caller, one float32 .npy per
+    output (rank r > 0 of a multi-GPU run writes <name>_rank<r>.npy: its own batch)."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in tensors.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float32)
+        np.save(os.path.join(d, name + (f"_rank{rank}" if world > 1 and rank else "") + ".npy"), a)
+
+
 def main():
     args = parse()
     # before any GPU call: this rank on its GPU's NUMA node (best effort; hostcpu.py); the mask
@@ -962,14 +1010,17 @@ def main():
                                 Wn["fc_policy.weight"], Wn["fc_policy.bias"],
                                 Wn["fc_value.weight"], Wn["fc_value.bias"], want_y=False)
 
-    # correctness guard: the bench path is bit-identical to the unfused calls and to the
-    # evaluator's predict_with_gnn path
+    # the first call (it caches the weights' split planes), outside the clock-settle window
     step()
-    _, pi_u, v_u, _ = step_unfused()
-    _, pi_ref, v_ref = ev.evaluate(boards, gnn=True)
     torch.cuda.synchronize()
-    assert torch.equal(pi, pi_u) and torch.equal(v, v_u)
-    assert torch.equal(pi, pi_ref) and torch.equal(v, v_ref)
+    # correctness guard (--full): the bench path is bit-identical to the unfused calls and to
+    # the evaluator's predict_with_gnn path
+    if args.full:
+        _, pi_u, v_u, _ = step_unfused()
+        _, pi_ref, v_ref = ev.evaluate(boards, gnn=True)
+        torch.cuda.synchronize()
+        assert torch.equal(pi, pi_u) and torch.equal(v, v_u)
+        assert torch.equal(pi, pi_ref) and torch.equal(v, v_ref)
 
     # the GPU's clock ramps over the first tens of ms of sustained work (DPM): before the W
     # warmup steps, full steps run until `--settle-ms` of wall time has passed, so that even a
@@ -998,6 +1049,15 @@ def main():
         t = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"logp": logp, "pi": pi, "v": v}, rank, world)
+    out = headline(args, world, B, elapsed, settle_ms, settle_steps)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # the dominant kernel's call, output_transform.0 as a standalone az_gemm_f32 (its own A
     # split + tile kernel + split-K reduce), HIP events per call on the stream it runs on
     feat = ops.c4_trunk(boards, Wn, out=featbuf)
@@ -1120,26 +1180,7 @@ def main():
                 "host": host}
 
     if rank == 0:
-        value = world * B * args.steps / elapsed
-        out = {
-            "metric": METRIC, "value": round(value, 1), "unit": "board evals/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "clock_settle": {"ms": round(settle_ms, 1), "steps": settle_steps,
-                             "note": "untimed full steps before the warmup (GPU clock ramp)"},
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 (fp16x2 row-scaled split, 3 products: output_transform GEMMs and the "
-                     "trunk's conv2 split each fp32 operand row, power-of-two scaled, into 2 fp16 "
-                     "terms, 3 fp16 MFMA products, fp32 accumulate; ~22-bit operands: "
-                     "tests/test_gpu_trained.py holds pi / v / log pi to 1e-5 of float64 and of "
-                     "the reference on its trained weights, margins reported)",
-            "data": "synthetic (uniform random {-1,0,1} 7x7 boards; PCG64 random-init weights "
-                    "of the reference shapes)",
-            "config": {"workload": "Connect4 (reference 7x7+pass board) Connect4GNN "
-                                   "predict_with_gnn per-board fwd: trunk -> output_transform "
-                                   "-> heads, batch of random boards per GPU",
-                       "global_batch": B * world, "batch_per_gpu": B, "feature_dim": F,
-                       "parallelism": f"dp{world} (independent shards, no collective)"},
+        out.update({
             "roofline": x3_roofline(
                 "az_gemm_f32 output_transform.0 as a standalone call (A's split into fp16 planes "
                 "+ row scales, tile kernel on W's cached planes, split-K reduce; timed apart from "
@@ -1162,7 +1203,7 @@ def main():
             # one-launch leaf kernel hand-over timeouts (azhip/wrappers.py; each switches an
             # evaluator to the four-launch path): non-zero means degraded batch-1 / arena legs
             "leaf_timeouts": _leaf_timeouts(),
-        }
+        })
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -4,7 +4,7 @@
 set -e
 tag=${1:-ab_engine}
 mkdir -p gpurun_out/$tag
-F="--steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
+F="--full --steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
 for i in 1 2 3; do
   for lib in base new; do
     if [ $lib = base ]; then export AZ_AB_MCTS_LIB=libaz_mcts_base.so; else unset AZ_AB_MCTS_LIB; fi

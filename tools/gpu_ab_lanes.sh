@@ -3,7 +3,7 @@
 set -e
 tag=${1:-ab_lanes}
 mkdir -p gpurun_out/$tag
-F="--steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
+F="--full --steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
 for i in 1 2; do
   for lanes in 2 3 4; do
     for lib in base new; do

@@ -4,7 +4,7 @@ set -e
 tag=${1:-ab_spstream}
 mkdir -p gpurun_out/$tag
 export OMP_WAIT_POLICY=passive
-F="--steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
+F="--full --steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
 for i in 1 2; do
   for mode in own:2 one:2 own:3 one:3 one:4; do
     st=${mode%%:*}; lanes=${mode##*:}

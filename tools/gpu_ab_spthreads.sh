@@ -4,7 +4,7 @@
 set -e
 tag=${1:-ab_spthreads}
 mkdir -p gpurun_out/$tag
-F="--steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
+F="--full --steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
 for i in 1 2; do
   for mode in 16 15 14 12 16p 15p; do
     th=${mode%p}

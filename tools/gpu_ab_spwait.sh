@@ -4,7 +4,7 @@ set -e
 tag=${1:-ab_spwait}
 mkdir -p gpurun_out/$tag
 cat /sys/fs/cgroup/cpu.max > gpurun_out/$tag/cpu_max.txt 2>&1 || true
-F="--steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
+F="--full --steps 5 --warmup 2 --no-cpu --no-train --no-b1 --no-grid --no-aggregate --no-agg-extra --large-batch 0"
 for i in 1 2; do
   for mode in base:16 new:16 new:16p new:14p base:16p; do
     lib=${mode%%:*}; th=${mode##*:}; n=${th%p}

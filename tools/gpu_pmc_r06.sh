@@ -13,7 +13,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-B="python3 bench.py --steps 5 --warmup 2 --settle-ms 0 --no-cpu --no-selfplay --no-train --no-agg-extra --no-grid --no-b1 --large-batch 0"
+B="python3 bench.py --full --steps 5 --warmup 2 --settle-ms 0 --no-cpu --no-selfplay --no-train --no-agg-extra --no-grid --no-b1 --large-batch 0"
 P="python3 tools/band_probe.py 512 3"
 PART=${2:-step}
 if [ "$PART" = step ]; then

@@ -9,7 +9,7 @@ O=gpurun_out/${1:-ab}
 mkdir -p $O
 V=${VARIANTS:-"base=libaz_hip_base.so new="}
 P="python -u tools/p2h_probe.py 512,800,1576,3150 100"
-B="python bench.py --steps 200 --warmup 20 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0"
+B="python bench.py --full --steps 200 --warmup 20 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0"
 for i in 1 2; do
   for v in $V; do
     n=${v%%=*}; l=${v#*=}

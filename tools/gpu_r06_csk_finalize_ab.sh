@@ -3,7 +3,7 @@
 # tests on the working tree's library.
 #   VARIANTS="base=libaz_hip_base.so new=" bash tools/gpu_r06_csk_finalize_ab.sh
 cd "$GRAFT_REPO_ROOT"
-B="bench.py --steps 5 --warmup 2 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0"
+B="bench.py --full --steps 5 --warmup 2 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0"
 for v in ${VARIANTS:-base=libaz_hip_base.so new=}; do
   n=${v%%=*}; l=${v#*=}
   AZ_AB_LIB=$l timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/cskfin/$n -o run -- python3 $B > gpurun_out/cskfin_$n.log 2>&1 || exit 1

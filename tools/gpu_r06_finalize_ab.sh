@@ -3,7 +3,7 @@
 # duration), then the presplit / kernel / trained GPU tests on the working tree's library.
 #   VARIANTS="base=libaz_hip_base.so new=" bash tools/gpu_r06_finalize_ab.sh
 cd "$GRAFT_REPO_ROOT"
-B="bench.py --steps 200 --warmup 20 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0 --no-selfplay"
+B="bench.py --full --steps 200 --warmup 20 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0 --no-selfplay"
 for v in ${VARIANTS:-base=libaz_hip_base.so new=}; do
   n=${v%%=*}; l=${v#*=}
   AZ_AB_LIB=$l timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/fin_prof/$n -o run -- python3 $B > gpurun_out/fin_prof_$n.log 2>&1 || exit 1

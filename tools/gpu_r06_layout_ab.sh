@@ -13,7 +13,7 @@ for i in 1 2; do
   timeout -k 10 180 $P > $O/p2h_new_$i.jsonl 2>&1 || exit 1
   AZ_TUNING_LIB=1 AZ_P3_RING=2 timeout -k 10 180 $P > $O/p2h_ring2_$i.jsonl 2>&1 || exit 1
 done
-B="python bench.py --steps 200 --warmup 20 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0"
+B="python bench.py --full --steps 200 --warmup 20 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0"
 for i in 1 2; do
   AZ_AB_LIB=libaz_hip_base.so timeout -k 10 300 $B > $O/bench_base_$i.log 2>&1 || exit 1
   timeout -k 10 300 $B > $O/bench_new_$i.log 2>&1 || exit 1

@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 R=gpurun_out/${1:-sw}; mkdir -p $R
 run() {   # name, env...
   local name=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0 > $R/sp_$name.json 2>> $R/err.txt
+  env "$@" timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0 > $R/sp_$name.json 2>> $R/err.txt
 }
 for i in 1 2 3; do
   run new_$i AZ_SP_SWITCH_INTERVAL=0.0002 || exit $?

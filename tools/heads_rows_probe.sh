@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/hrows
 mkdir -p $O
-Q="--no-cpu --no-selfplay --no-train --no-aggregate --no-grid --large-batch 0"
+Q="--full --no-cpu --no-selfplay --no-train --no-aggregate --no-grid --large-batch 0"
 for r in 16 8 4 16 8 4; do
   AZ_SPLITK_HEADS_ROWS=$r timeout -k 10 120 python bench.py --steps 200 --warmup 20 $Q > $O/b$r.json 2> $O/b$r.err || exit $?
   python -c "import json;d=json.load(open('$O/b$r.json'));print($r, d['value'], d['ms_per_step'])"

@@ -80,7 +80,7 @@ def main(d, tag):
     res = {
         "round": 1, "tag": tag,
         "source": f"rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes) over "
-                  f"`python3 bench.py --steps 5 --warmup 2 --no-cpu --no-selfplay --no-train` "
+                  f"`python3 bench.py --full --steps 5 --warmup 2 --no-cpu --no-selfplay --no-train` "
                   f"(tools/gpu_profile.sh {tag}); per-kernel averages over all dispatches; "
                   f"bytes = (2*FETCH_SIZE + WRITE_SIZE) KB * 1024 (gfx950 FETCH_SIZE reports "
                   f"half of wide reads, MI355X_MICROARCH.md HBM section)",
