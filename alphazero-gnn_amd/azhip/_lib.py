@@ -75,6 +75,17 @@ class C4Eval(ctypes.Structure):
                 ("ws_bytes", c_size_t), ("sync", c_void_p), ("err", c_void_p)]
 
 
+class TttEval(ctypes.Structure):
+    """az_ttt_eval (include/az_hip.h)."""
+    _fields_ = ([(f"{l}_{k}", c_void_p) for l in ("conv1", "conv2", "conv3", "fc1", "fc2",
+                                                    "fc_policy", "fc_value") for k in "wb"] +
+                [("n", c_int), ("A", c_int), ("F", c_int),
+                 ("ot0_w", c_void_p), ("ot0_b", c_void_p), ("ot2_w", c_void_p),
+                 ("ot2_b", c_void_p), ("max_B", c_int), ("feat", c_void_p), ("h1", c_void_p),
+                 ("h2", c_void_p), ("hidden", c_void_p), ("y", c_void_p), ("logp", c_void_p),
+                 ("glogp", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t)])
+
+
 # name -> (restype, argtypes); every symbol here must be declared in include/az_hip.h
 SIGNATURES = {
     "az_abi_version": (c_int, []),
@@ -90,6 +101,11 @@ SIGNATURES = {
     "az_heads_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "az_c4_eval_fwd": (c_int, [ctypes.POINTER(C4Eval), c_void_p, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
+    "az_ttt_trunk_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "az_ttt_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "az_ttt_eval_fwd": (c_int, [ctypes.POINTER(TttEval), c_void_p, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
     "az_c4_trunk_heads_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -123,6 +123,16 @@ class TicTacToeNet(_Net):
         self.training = True
 
     def features(self, b):
+        """b: int8 [B,n,n] -> [B, 128 (n-2)^2] (TicTacToeNet.py:33-36): the one-launch trunk on
+        the boards it covers (n = 3..5), bit-identical to features_eager."""
+        if 3 <= self.n <= 5:
+            W = self.params
+            W.sync()
+            return ops.ttt_trunk(b, W)
+        return self.features_eager(b)
+
+    def features_eager(self, b):
+        """The three conv3x3_relu launches (any n)."""
         W = self.params
         W.sync()
         s = ops.conv3x3_relu(b, W["conv1.weight"], W["conv1.bias"], 1)

@@ -250,6 +250,59 @@ def conv3x3_relu(x, w, b, pad, out=None):
     return out
 
 
+def ttt_trunk(boards_i8, W, out=None):
+    """TicTacToeNet conv1..conv3 (+ ReLU) in one launch (az_ttt_trunk_fwd): int8 boards
+    [B,n,n], n in 3..5 -> features [B, 128 (n-2)^2], bit-identical to three conv3x3_relu calls."""
+    _need(boards_i8, torch.int8, "boards")
+    B, n = boards_i8.shape[0], boards_i8.shape[1]
+    if out is None:
+        out = torch.empty((B, 128 * (n - 2) * (n - 2)), device=_dev(boards_i8),
+                          dtype=torch.float32)
+    L = _lib.lib()
+    _lib.check(L.az_ttt_trunk_fwd(_p(boards_i8), B, n, _p(W["conv1.weight"]), _p(W["conv1.bias"]),
+                                  _p(W["conv2.weight"]), _p(W["conv2.bias"]),
+                                  _p(W["conv3.weight"]), _p(W["conv3.bias"]), _p(out), _stream()),
+               "az_ttt_trunk_fwd")
+    return out
+
+
+class TttEval:
+    """az_ttt_eval descriptor with its device scratch for up to max_B boards of an n x n
+    TicTacToeNet: W the net's parameter tensors, G the PolicyValueGNN's (None: no GNN tail).
+    The tensors are read through the pointers taken here, so they must be updated in place."""
+
+    def __init__(self, W, G, n, A, max_B, device):
+        F = 128 * (n - 2) * (n - 2)
+        self.n, self.A, self.F, self.max_B = n, A, F, max_B
+        e = lambda *s: torch.empty(s, device=device, dtype=torch.float32)  # noqa: E731
+        self.feat, self.h1, self.h2 = e(max_B, F), e(max_B, 512), e(max_B, 512)
+        self.hidden = e(max_B, F) if G is not None else None
+        self.y = e(max_B, F) if G is not None else None
+        self.logp, self.glogp = e(max_B, A), e(max_B, A)
+        nb = int(_lib.lib().az_ttt_eval_ws_bytes(max_B, n, A))
+        if nb == 0:
+            raise ValueError(f"az_ttt_eval: unsupported shape n={n} A={A} max_B={max_B}")
+        self.ws = torch.empty((nb,), dtype=torch.uint8, device=device)
+        P = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        ot = [P(G[f"output_transform.{i}.{k}"]) if G is not None else None
+              for i in (0, 2) for k in ("weight", "bias")]
+        self.desc = _lib.TttEval(
+            *[P(W[f"{l}.{k}"]) for l in ("conv1", "conv2", "conv3", "fc1", "fc2", "fc_policy",
+                                         "fc_value") for k in ("weight", "bias")],
+            n, A, F, *ot, max_B, P(self.feat), P(self.h1), P(self.h2), P(self.hidden), P(self.y),
+            P(self.logp), P(self.glogp), P(self.ws), self.ws.numel())
+        self._keep = (W, G)
+
+
+def ttt_eval(ev, boards_i8, B, pi=None, v=None, gpi=None, gv=None, stream=None):
+    """az_ttt_eval_fwd on `ev` (a TttEval): the first B boards -> pi / v (standard heads) and
+    gpi / gv (GNN tail), each written when given; device tensors or HostBuffer views.  Queued on
+    `stream` (default: the current stream); nothing is synchronised."""
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(_lib.lib().az_ttt_eval_fwd(ctypes.byref(ev.desc), _p(boards_i8), B, _p(pi), _p(v),
+                                          _p(gpi), _p(gv), s), "az_ttt_eval_fwd")
+
+
 def heads(hp, wp, bp, wv, bv, hv=None, want_pi=True, logp=None, pi=None, v=None):
     """logp = log_softmax(hp wp^T + bp); v = tanh(hv wv^T + bv) (hv defaults to hp)."""
     hv = hp if hv is None else hv

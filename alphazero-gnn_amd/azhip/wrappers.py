@@ -100,6 +100,7 @@ class _DirectBatch:
         self.w, self.cap, self.ring = w, 0, []
         self.stream = stream      # None: the current stream; else this stream (own scratch)
         self.fn = _lib.lib().az_c4_eval_fwd
+        self.fn_name = "az_c4_eval_fwd"
 
     def _grow(self, n):
         w, dev, A, F = self.w, self.w.device, self.w.action_size, 3136
@@ -156,10 +157,31 @@ class _DirectBatch:
         rc = self.fn(ctypes.byref(self.desc), ctypes.c_void_p(hin.data_ptr()), n, P(pi), P(v),
                      P(gpi), P(gv), ctypes.c_void_p(s.cuda_stream))
         if rc:
-            _lib.check(rc, "az_c4_eval_fwd")
+            _lib.check(rc, self.fn_name)
         ev = torch.cuda.Event()
         ev.record(s)
         return _PendingDirect(e, (pi, v, gpi, gv), ev, n)
+
+
+class _TttDirectBatch(_DirectBatch):
+    """_DirectBatch for the TicTacToeNet (n = 3..5): ONE az_ttt_eval_fwd call per batch, same
+    host ring, same ownership tokens.  Without a GNN (the CNN-only wrapper) only `both=False`
+    batches exist and the descriptor carries no output_transform."""
+
+    def __init__(self, w, stream=None):
+        super().__init__(w, stream)
+        self.fn = _lib.lib().az_ttt_eval_fwd
+        self.fn_name = "az_ttt_eval_fwd"
+
+    def _grow(self, n):
+        w = self.w
+        cap = max(1024, 1 << (int(n) - 1).bit_length())
+        torch.cuda.synchronize(w.device)          # in-flight batches may use the old scratch
+        self.ev = ops.TttEval(w.nnet.params, w.gnn.params if w.has_gnn else None, w.nnet.n,
+                              w.action_size, cap, w.device)
+        self.desc = self.ev.desc
+        self.ring = []        # entries still held by unread predictions keep their buffers
+        self.cap = cap
 
 
 class _PinnedRing:
@@ -334,6 +356,7 @@ class _Batch1Direct:
         self.args = (ctypes.byref(self.desc), ctypes.c_void_p(self.h_in.data_ptr()))
         self.outs = tuple(None if v is None else ctypes.c_void_p(v.ctypes.data) for v in views)
         self.fn = L.az_c4_eval_fwd
+        self.fn_name = "az_c4_eval_fwd"
         self.dev = dev
         # the stream current at construction (the default stream, where train() updates the
         # parameters) serves every call: torch.cuda.current_stream() costs ~2.7 us per call
@@ -348,7 +371,7 @@ class _Batch1Direct:
         s = self.stream
         rc = self.fn(*self.args, n, *self.outs, self.sptr)
         if rc:
-            _lib.check(rc, "az_c4_eval_fwd")
+            _lib.check(rc, self.fn_name)
         s.synchronize()
         if self.err_np is not None and self.err_np[0]:
             # the one-launch form's hand-over timed out (its blocks were not all resident, e.g.
@@ -384,10 +407,58 @@ class _Batch1Direct:
         return tuple(None if v is None else v[:n].copy() for v in self.views)
 
 
+class _TttBatch1Direct(_Batch1Direct):
+    """_Batch1Direct for the TicTacToeNet (n = 3..5): up to `cap` boards as ONE az_ttt_eval_fwd
+    call (4 launches for std, 6 for gnn / both; no in-kernel hand-over, so no timeout path).
+    Same host layout, run() and run_rows() as the Connect4 evaluator."""
+
+    def __init__(self, w, kind, cap=1):
+        dev = w.device
+        A = w.action_size
+        self.kind, self.A, self.cap = kind, A, cap
+        std = kind in ("std", "both")
+        gnn = kind in ("gnn", "both")
+        width = (A + 1) * (int(std) + int(gnn))
+        self.host = ops.HostBuffer(256 * cap + 4 * width * cap)
+        self.h_in = self.host.view(0, torch.int8, (cap, w.board_x, w.board_y))
+        self.h_out = self.host.view(256 * cap, torch.float32, (cap * width,))
+        self.ev = ops.TttEval(w.nnet.params, w.gnn.params if gnn else None, w.nnet.n, A, cap, dev)
+        self.desc = self.ev.desc
+        self.err_np = None
+        o = self.h_out.numpy()
+        # views: pi [cap][A], v [cap], gpi [cap][A], gv [cap] (None where the kind has none)
+        off, views = 0, []
+        for on in (std, gnn):
+            if on:
+                views += [o[off:off + cap * A].reshape(cap, A), o[off + cap * A:off + cap * (A + 1)]]
+                off += cap * (A + 1)
+            else:
+                views += [None, None]
+        self.views = views
+        self.args = (ctypes.byref(self.desc), ctypes.c_void_p(self.h_in.data_ptr()))
+        self.outs = tuple(None if v is None else ctypes.c_void_p(v.ctypes.data) for v in views)
+        self.fn = _lib.lib().az_ttt_eval_fwd
+        self.fn_name = "az_ttt_eval_fwd"
+        self.dev = dev
+        self.stream = torch.cuda.current_stream(dev)
+        self.sptr = ctypes.c_void_p(self.stream.cuda_stream)
+        self.h_in_np = self.h_in.numpy()
+        self.h_out_np = self.h_out.numpy()
+
+
+def _is_c4(w):
+    return isinstance(w.nnet, nets.Connect4Net) and w.nnet.n == 7
+
+
+def _is_ttt(w):
+    return isinstance(w.nnet, nets.TicTacToeNet) and 3 <= w.nnet.n <= 5
+
+
 def _direct_ok(w):
-    """az_c4_eval_fwd covers the 7x7 Connect4Net (+ PolicyValueGNN output_transform)."""
+    """az_c4_eval_fwd covers the 7x7 Connect4Net (+ PolicyValueGNN output_transform),
+    az_ttt_eval_fwd the TicTacToeNet on 3x3 .. 5x5 boards."""
     return (os.environ.get("AZ_B1_MODE", "direct") == "direct"
-            and isinstance(w.nnet, nets.Connect4Net) and w.nnet.n == 7
+            and (_is_c4(w) or _is_ttt(w))
             and os.environ.get("AZ_NO_ZEROCOPY", "0") in ("", "0"))
 
 
@@ -443,7 +514,8 @@ class NetWrapper:
             if self.has_gnn:
                 self.gnn.eval()
             if _direct_ok(self):
-                g[kind] = _Batch1Direct(self, kind, cap=8 if kind == "both" else 1)
+                cls = _TttBatch1Direct if _is_ttt(self) else _Batch1Direct
+                g[kind] = cls(self, kind, cap=8 if kind == "both" else 1)
             else:
                 g[kind] = _Batch1Graph(self, kind)
         return g[kind]
@@ -487,14 +559,16 @@ class NetWrapper:
         each lane a stream, so one lane's batch can overlap the other's on the GPU); the caller
         orders the stream after any parameter update (play_episodes_engine does)."""
         self._sync_params()
-        if self.has_gnn and _direct_ok(self) and len(boards) > 0:
+        if (self.has_gnn or _is_ttt(self)) and _direct_ok(self) and len(boards) > 0:
             directs = self.__dict__.setdefault("_directs", {})
             key = None if stream is None else stream.cuda_stream
             d = directs.get(key)
             if d is None:
-                d = directs[key] = _DirectBatch(self, stream)
+                cls = _TttDirectBatch if _is_ttt(self) else _DirectBatch
+                d = directs[key] = cls(self, stream)
             self.nnet.eval()
-            self.gnn.eval()
+            if self.has_gnn:
+                self.gnn.eval()
             return d.launch(boards, both)
         if not hasattr(self, "_ring"):
             self._ring = _PinnedRing()
@@ -732,8 +806,9 @@ class GNNWrapperMixin:
     @property
     def batch_invariant_rows(self):
         """Largest batch whose predict_both rows are bit-identical to batch-1 calls: the 7x7
-        Connect4 evaluator (az_c4_eval_fwd) computes every row of a batch of <= 8 with the
-        batch-1 arithmetic (tests/test_gpu_selfplay.py); 0 = no such guarantee."""
+        Connect4 evaluator (az_c4_eval_fwd) and the TicTacToe one (az_ttt_eval_fwd, n = 3..5)
+        compute every row of a batch of <= 8 with the batch-1 arithmetic
+        (tests/test_gpu_selfplay.py, tests/test_gpu_ttt_eval.py); 0 = no such guarantee."""
         return 8 if _direct_ok(self) else 0
 
     def predict(self, board):

@@ -2862,6 +2862,39 @@ __global__ __launch_bounds__(256) void gemv_side_heads(GemmArgs p, SideHeads h, 
   }
 }
 
+// Two or three whole-K GEMVs over the SAME M <= 8 rows of A in one grid (az_ttt_eval_fwd: fc1 and
+// fc2 of the TicTacToe heads, plus output_transform.0 for predict_both -- independent weight
+// streams that all read the trunk's features).  Blocks [0, nblk0) run p as it stands, the next
+// o1.nblk blocks run it with o1's weights / epilogue / output, the rest with o2's; a block is
+// gemv_full_block / gemv_rows_block unchanged, so every output is the lane-strided fmaf chain +
+// wave_sum that az_gemm_f32 gives for the same M and K.  No block waits for another.
+struct GemvOut {
+  const float* W; int ldb;
+  const float* bias; int act;
+  float* C; int ldc;
+  int N, nblk;
+};
+
+template <int MK, int S>   // MK: 1 / 2 / 4 / 8 = gemv_full_block rows, 0 = gemv_rows_block (2 per group)
+__global__ __launch_bounds__(256) void gemv_multi(GemmArgs p, GemvOut o1, GemvOut o2, int nblk0) {
+  __shared__ __attribute__((aligned(16))) float As[(MK == 0 ? 2 : MK) * S * 256];
+  int b = blockIdx.x;
+  if (b >= nblk0) {
+    b -= nblk0;
+    const bool second = b >= o1.nblk;
+    if (second) b -= o1.nblk;
+    p.B = second ? o2.W : o1.W;
+    p.ldb = second ? o2.ldb : o1.ldb;
+    p.bias = second ? o2.bias : o1.bias;
+    p.act = second ? o2.act : o1.act;
+    p.C = second ? o2.C : o1.C;
+    p.ldc = second ? o2.ldc : o1.ldc;
+    p.N = second ? o2.N : o1.N;
+  }
+  if constexpr (MK == 0) gemv_rows_block<S, 2, 2>(p, b, As);
+  else gemv_full_block<MK, S, 2>(p, b, As);
+}
+
 // --------------------------------------------------------------------- the batch-1 leaf kernel
 // az_c4_eval_fwd for B <= 2 boards (the MCTS leaf, MCTS.py:169-173, and the arena's two-row
 // speculative batches; 3-8 rows are faster as four launches) in ONE launch instead of four (trunk, output_transform.0 + standard heads,
@@ -4643,6 +4676,54 @@ int gemv1_with_side_heads(const az_gemm_desc* d, const SideHeads* h, hipStream_t
   else if (a.M == 2) hipLaunchKernelGGL((gemv_side_heads<13, 2, 2>), grid, blk, 0, s, a, *h, nblk);
   else hipLaunchKernelGGL((gemv_side_heads<13, 2, 3>), grid, blk, 0, s, a, *h, nblk);
   const int rc = check_launch("gemv_side_heads");
+  return rc == AZ_OK ? 1 : rc;
+}
+
+// gemv_multi: d0, d1 and (nullable) d2 must share M <= 8, K, A and lda, with K-major operands and
+// a plain bias / activation epilogue.  The kernel per (M, K) is the one launch_gemv picks for a
+// single GEMV of that shape (gemv_full<MR, S, 2>), except M = 5..8 at 1024 < K <= 2048, where
+// launch_gemv's chunked gemv_f32<8> gives way to gemv_rows_block<8, 2, 2>: the same lane-strided
+// chain (chunk c, step s of the chunked kernel is step 4c + s of the whole-K one; k past K meets
+// zeros in the staged A in both).  Returns 1 when launched, 0 when the shapes do not qualify
+// (nothing launched), or a negative AZ_E* code.
+int gemv_multi_fwd(const az_gemm_desc* d0, const az_gemm_desc* d1, const az_gemm_desc* d2,
+                   hipStream_t s) {
+  const az_gemm_desc* ds[3] = {d0, d1, d2};
+  const int nd = d2 ? 3 : 2;
+  if (!d0 || !d1) return 0;
+  for (int i = 0; i < nd; ++i) {
+    const az_gemm_desc* d = ds[i];
+    if (!(d->M >= 1 && d->M <= 8 && d->M == d0->M && d->K == d0->K && d->A == d0->A &&
+          d->lda == d0->lda && d->a_kmajor && d->b_kmajor && !d->A2 && !d->a_rows && !d->b_rows &&
+          !d->C2 && !d->R && !d->G && !d->c_rows && d->beta == 0.f && d->act >= AZ_ACT_NONE &&
+          d->act <= AZ_ACT_TANH && d->N >= 1 && d->K >= 4 && d->K % 4 == 0 && d->lda % 4 == 0 &&
+          d->ldb % 4 == 0 && d->A && d->B && d->C && aligned16(d->A) && aligned16(d->B)))
+      return 0;
+  }
+  GemmArgs a = {};
+  a.M = d0->M; a.N = d0->N; a.K = d0->K;
+  a.A = d0->A; a.lda = d0->lda; a.K0 = d0->K;
+  a.B = d0->B; a.ldb = d0->ldb;
+  a.bias = d0->bias; a.act = d0->act; a.C = d0->C; a.ldc = d0->ldc;
+  a.splits = 1; a.kc = d0->K;
+  GemvOut o[2] = {};
+  for (int i = 1; i < nd; ++i)
+    o[i - 1] = {ds[i]->B, ds[i]->ldb, ds[i]->bias, ds[i]->act, ds[i]->C, ds[i]->ldc, ds[i]->N,
+                (ds[i]->N + 7) / 8};
+  const int nblk0 = (a.N + 7) / 8;
+  const dim3 grid(nblk0 + o[0].nblk + o[1].nblk), blk(256);
+  const int mr = a.M == 1 ? 1 : a.M == 2 ? 2 : a.M <= 4 ? 4 : 8;
+  const int S = a.K <= 256 ? 1 : a.K <= 512 ? 2 : a.K <= 1024 ? 0 : a.K <= 2048 ? 8 : 0;
+  switch (S * 16 + mr) {
+#define AZ_GM(SS, MM, MK) case SS * 16 + MM: hipLaunchKernelGGL((gemv_multi<MK, SS>), grid, blk, 0, s, a, \
+                                                                o[0], o[1], nblk0); break;
+    AZ_GM(1, 1, 1) AZ_GM(1, 2, 2) AZ_GM(1, 4, 4) AZ_GM(1, 8, 8)
+    AZ_GM(2, 1, 1) AZ_GM(2, 2, 2) AZ_GM(2, 4, 4) AZ_GM(2, 8, 8)
+    AZ_GM(8, 1, 1) AZ_GM(8, 2, 2) AZ_GM(8, 4, 4) AZ_GM(8, 8, 0)
+#undef AZ_GM
+    default: return 0;
+  }
+  const int rc = check_launch("gemv_multi");
   return rc == AZ_OK ? 1 : rc;
 }
 

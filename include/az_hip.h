@@ -182,6 +182,60 @@ typedef struct az_c4_eval {
 int az_c4_eval_fwd(const az_c4_eval* e, const int8_t* boards, int B, float* pi, float* v,
                    float* gpi, float* gv, void* stream);
 
+/* TicTacToeNet trunk, tictactoe/TicTacToeNet.py:33-36 (== TicTacToeGNNWrapper.extract_features,
+ * TicTacToeGNN.py:25-34): conv1 3x3 p1 + ReLU -> conv2 3x3 p1 + ReLU -> conv3 3x3 p0 + ReLU ->
+ * NCHW flatten in ONE launch, one workgroup per board, both intermediate planes in LDS.  Every
+ * output is the fmaf chain of az_conv3x3_relu_fwd ((ci, kh, kw) order, out-of-range taps skipped,
+ * + bias, ReLU), so feat is bit-identical to the three az_conv3x3_relu_fwd calls.
+ *   boards  int8 [B][n][n] in {-1,0,1}, n in {3, 4, 5} (may be az_host_alloc memory)
+ *   feat    fp32 [B][128 (n-2)^2] */
+int az_ttt_trunk_fwd(const int8_t* boards, int B, int n, const float* conv1_w,
+                     const float* conv1_b, const float* conv2_w, const float* conv2_b,
+                     const float* conv3_w, const float* conv3_b, float* feat, void* stream);
+
+/* The whole TicTacToe leaf evaluation of MCTS.search (MCTS.py:169-174 via TicTacToeGNN.py:47-110:
+ * predict and predict_with_gnn of the same boards) as ONE host call with direct launches, no
+ * launch waiting on another inside a kernel:
+ *   az_ttt_trunk_fwd;  h1 = relu(fc1 feat), h2 = relu(fc2 feat);  az_heads_fwd(h1, h2)   (v)
+ *   hidden = relu(ot0 feat);  y = ot2 hidden;  h1 / h2 of y;  az_heads_fwd(h1, h2)       (gv)
+ * Up to 8 rows, fc1 and fc2 -- and output_transform.0 when both v and gv are asked for -- share
+ * one launch (two / three weight streams over the same rows, each output the GEMV arithmetic
+ * az_gemm_f32 has at M <= 8): 4 launches for v, 6 for gv, 6 for both.  That arithmetic does not
+ * depend on the number of rows, so a row of a batch of <= 8 is bit-identical to the same board
+ * evaluated alone.  Above 8 rows every linear layer is az_gemm_f32 on the rest of the workspace.
+ * At every B the outputs are bit-identical to az_conv3x3_relu_fwd x 3, az_gemm_f32 and az_heads_fwd
+ * called one by one (the eager path was found row-invariant at 2..8 rows, so no shape needs a
+ * weaker statement). */
+typedef struct az_ttt_eval {
+  const float* conv1_w; const float* conv1_b; const float* conv2_w; const float* conv2_b;
+  const float* conv3_w; const float* conv3_b;
+  const float* fc1_w; const float* fc1_b;  /* [512][F], [512] */
+  const float* fc2_w; const float* fc2_b;
+  const float* fc_policy_w; const float* fc_policy_b;  /* [A][512], [A] */
+  const float* fc_value_w; const float* fc_value_b;    /* [1][512], [1] */
+  int n;                                   /* board side, 3..5 */
+  int A;                                   /* actions (fc_policy rows), <= 32 */
+  int F;                                   /* 128 (n-2)^2 */
+  const float* ot0_w; const float* ot0_b;  /* output_transform.0 [F][F], [F] */
+  const float* ot2_w; const float* ot2_b;  /* output_transform.2; all four NULL: no GNN tail */
+  int max_B;                               /* capacity of the scratch below */
+  float* feat;                             /* device [max_B][F] */
+  float* h1; float* h2;                    /* device [max_B][512] each */
+  float* hidden; float* y;                 /* device [max_B][F] each (GNN tail only) */
+  float* logp; float* glogp;               /* device [max_B][A] */
+  void* ws; size_t ws_bytes;               /* >= az_ttt_eval_ws_bytes(max_B, n, A) */
+} az_ttt_eval;
+/* Workspace for the descriptor: the heads' partials and, above 8 rows, room for every split-K
+ * plan az_gemm_f32 makes for these layers (so its plans are those of a large workspace).
+ * 0 for a shape az_ttt_eval_fwd rejects. */
+size_t az_ttt_eval_ws_bytes(int max_B, int n, int A);
+/* v != NULL: standard heads into pi [B][A] (may be NULL) and v [B];  gv != NULL: the GNN tail
+ * into gpi / gv; at least one of them.  boards, pi, v, gpi, gv may be az_host_alloc memory.
+ * 1 <= B <= max_B.  A bad shape (n outside 3..5, A > 32, F != 128 (n-2)^2, B), a null pointer
+ * or a small workspace returns AZ_EINVAL before anything is launched. */
+int az_ttt_eval_fwd(const az_ttt_eval* e, const int8_t* boards, int B, float* pi, float* v,
+                    float* gpi, float* gv, void* stream);
+
 /* Per-row GNN evaluation tail: output_transform then the heads, i.e. gnn_utils.py:115 (in the
  * 1-row form of Connect4GNN.py:108-111, where the layers are the identity, gnn_utils.py:35-36)
  * followed by Connect4GNN.py:48-57 -- the batched predict_with_gnn after extract_features:
