@@ -232,8 +232,21 @@ class MCTS:
         path = []                     # (s, a) edges taken from the root
         board = canonicalBoard
         two_player = bool(getattr(self.game, "is_two_player", False))
+        on_path = set()               # single-player games only: the states of this descent
         while True:
             s = self.game.stringRepresentation(board)
+            if not two_player:
+                # A single-player board can come back to a state this descent already passed
+                # (FrozenLake: right, then left).  No statistic changes before the back-up, so
+                # the same moves would be chosen again for ever: the reference's recursive
+                # search ends there in a RecursionError.  The descent stops instead and backs up
+                # a neutral 0, like a state without a valid action.  (A game object without an
+                # is_two_player attribute counts as single-player here, as it already does for
+                # the sign of the back-up; Connect4 and TicTacToe set it to True.)
+                if s in on_path:
+                    v = 0
+                    break
+                on_path.add(s)
             if s not in self.Es:
                 self.Es[s] = self.game.getGameEnded(board, 1)
             if self.Es[s] != 0:

@@ -86,6 +86,23 @@ class TttEval(ctypes.Structure):
                  ("glogp", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t)])
 
 
+FL_MAX_LAYERS = 4
+
+
+class FlParams(ctypes.Structure):
+    """az_fl_params (include/az_hip.h): FrozenLakeNet tensors in state_dict order."""
+    _fields_ = [("fe0_w", c_void_p), ("fe0_b", c_void_p), ("fe2_w", c_void_p), ("fe2_b", c_void_p),
+                ("gnn_w", c_void_p * FL_MAX_LAYERS), ("gnn_b", c_void_p * FL_MAX_LAYERS),
+                ("policy_w", c_void_p), ("policy_b", c_void_p), ("value_w", c_void_p),
+                ("value_b", c_void_p)]
+
+
+class FlEval(ctypes.Structure):
+    """az_fl_eval (include/az_hip.h)."""
+    _fields_ = [("S", c_int), ("E", c_int), ("L", c_int), ("A", c_int), ("H", c_int),
+                ("max_B", c_int), ("w", FlParams)]
+
+
 # name -> (restype, argtypes); every symbol here must be declared in include/az_hip.h
 SIGNATURES = {
     "az_abi_version": (c_int, []),
@@ -106,6 +123,14 @@ SIGNATURES = {
     "az_ttt_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "az_ttt_eval_fwd": (c_int, [ctypes.POINTER(TttEval), c_void_p, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    "az_fl_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "az_fl_eval_fwd": (c_int, [ctypes.POINTER(FlEval), c_void_p, c_void_p, c_int, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
+    "az_fl_grads": (c_int, [ctypes.POINTER(FlEval), c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                            ctypes.POINTER(FlParams), c_void_p, c_void_p, c_void_p, c_size_t,
+                            c_void_p]),
+    "az_clip_grad_norm": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_int64), c_int,
+                                  c_float, c_void_p, c_void_p]),
     "az_c4_trunk_heads_fwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

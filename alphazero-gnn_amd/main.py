@@ -75,9 +75,13 @@ def get_checkpoint_path(game_name, filename, use_gnn=False, base_path="./checkpo
 
 
 def create_game_instance(GameClass, args):
-    """main.py:140-156 for the two registered games."""
+    """main.py:140-156 for the registered games."""
     if args.game == "tictactoe":
         return GameClass(n=args.board_size)
+    if args.game == "frozenlake":
+        return GameClass(map_size=args.board_size, custom_map=args.get("custom_map", None),
+                         is_slippery=args.get("is_slippery", False),
+                         render_mode=args.get("render_mode", None))
     if args.game == "connect4":
         return GameClass(board_size=args.board_size)
     return GameClass(**{k: v for k, v in args.items()

@@ -1,5 +1,5 @@
 """Game registry (reference register.py:1-79): name -> (Game, standard net, GNN net).
-FrozenLake (gymnasium, no GNN) is not registered: out of scope."""
+FrozenLake has no separate GNN version (its one net carries its own message passing)."""
 
 GAME_REGISTRY = {}
 
@@ -40,3 +40,8 @@ from connect4.Connect4Net import Connect4NNetWrapper  # noqa: E402
 from connect4.Connect4GNN import Connect4GNNWrapper  # noqa: E402
 
 register_game("connect4", Connect4Game, Connect4NNetWrapper, Connect4GNNWrapper)
+
+from frozenlake.FrozenLakeGame import FrozenLakeGame  # noqa: E402
+from frozenlake.FrozenLakeNet import FrozenLakeNet  # noqa: E402
+
+register_game("frozenlake", FrozenLakeGame, FrozenLakeNet)

@@ -236,6 +236,67 @@ size_t az_ttt_eval_ws_bytes(int max_B, int n, int A);
 int az_ttt_eval_fwd(const az_ttt_eval* e, const int8_t* boards, int B, float* pi, float* v,
                     float* gpi, float* gv, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * FrozenLakeNet (frozenlake/FrozenLakeNet.py:253-335): a leaf is a list of n = 1..5 node boards
+ * (the board itself, then the next state of every valid action), S = N*N floats each:
+ *   h_j  = relu(fe2 relu(fe0 x_j))                       feature_extractor, per node, hidden 128
+ *   r_1  = relu(c (W_1 sum_j h_j + n b_1))               GNN layer 1 under the all-ones adjacency
+ *   r_l  = relu(c n (W_l r_{l-1} + b_l))   l = 2..L      (every node row is the same from here on)
+ *   pi = softmax(policy_head r_L),  v = tanh(value_head r_L)
+ * with c = fp32(n^-1/2) * fp32(n^-1/2), the entry of the symmetrically normalised adjacency
+ * (FrozenLakeNet.py:55-74).  Only node 0's row reaches the heads, and it equals every other row.
+ * --------------------------------------------------------------------------------- */
+#define AZ_FL_MAX_NODES 5
+#define AZ_FL_MAX_LAYERS 4
+#define AZ_FL_HIDDEN 128
+/* One pointer per tensor in state_dict order; the same struct holds weights or their gradients. */
+typedef struct az_fl_params {
+  float* fe0_w; float* fe0_b;              /* feature_extractor.0 [128][S], [128] */
+  float* fe2_w; float* fe2_b;              /* feature_extractor.2 [E][128], [E] */
+  float* gnn_w[AZ_FL_MAX_LAYERS];          /* gnn_layers.i.W.weight [E][E]; entries >= L unused */
+  float* gnn_b[AZ_FL_MAX_LAYERS];          /* gnn_layers.i.W.bias [E] */
+  float* policy_w; float* policy_b;        /* policy_head [A][E], [A] */
+  float* value_w; float* value_b;          /* value_head [1][E], [1] */
+} az_fl_params;
+typedef struct az_fl_eval {
+  int S;                                   /* cells, N*N with N = 2..8 (<= 64) */
+  int E;                                   /* embedding_dim, 64 or 128 */
+  int L;                                   /* gnn_layers, 1..4 */
+  int A;                                   /* actions, 4 */
+  int H;                                   /* hidden size of the feature extractor, 128 */
+  int max_B;                               /* most leaves one call may carry */
+  az_fl_params w;                          /* weights; fe2_w and gnn_w need 16-byte alignment */
+} az_fl_eval;
+/* Bytes of device workspace az_fl_grads needs for max_B leaves (az_fl_eval_fwd keeps its
+ * intermediates in LDS and needs none); 0 for a shape the entry points reject. */
+size_t az_fl_eval_ws_bytes(int max_B, int S, int E, int L);
+/* predict of B leaves in ONE launch, one workgroup per leaf: nodes f32 [B][5][S] (rows at and
+ * beyond counts[b] are never read), counts i32 [B] in 1..5 (a value outside is clamped into it),
+ * pi [B][A], v [B].  Every output is a fixed-order fmaf chain over that leaf's nodes and the
+ * weights; no atomics, nothing shared between leaves: row b is bit-identical to the same leaf
+ * evaluated alone at every B.  nodes / counts / pi / v may be az_host_alloc memory.  ws is unused
+ * and may be NULL.  A null descriptor, B outside 1..max_B, S / E / L / A / H out of range or a
+ * null pointer returns AZ_EINVAL before any HIP call. */
+int az_fl_eval_fwd(const az_fl_eval* e, const float* nodes, const int* counts, int B, float* pi,
+                   float* v, void* ws, void* stream);
+/* Gradients of FrozenLakeNet.train's loss (FrozenLakeNet.py:157-160) over a batch of B leaves,
+ *   loss = -1/B sum_b sum_a tpi[b][a] log(max(pi[b][a], 1e-8)) + 1/B sum_b (v[b] - tv[b])^2,
+ * into one buffer per parameter (g, overwritten) and *loss (device).  Where pi < 1e-8 the clamp
+ * passes no gradient (unlike az_heads_loss_bwd, which differentiates log-softmax).  dlogits
+ * (nullable, [B][A]) receives dloss/dlogits.  Two launches: per-leaf forward + backward to the
+ * layer deltas (in ws), then one grid that sums delta^T input over leaves in leaf order for every
+ * weight (and the loss in a block of its own); no atomics, so two calls give equal bits.
+ * ws >= az_fl_eval_ws_bytes(max_B, S, E, L). */
+int az_fl_grads(const az_fl_eval* e, const float* nodes, const int* counts, int B,
+                const float* target_pi, const float* target_v, const az_fl_params* g, float* loss,
+                float* dlogits, void* ws, size_t ws_bytes, void* stream);
+/* torch.nn.utils.clip_grad_norm_ (FrozenLakeNet.py:166): the L2 norm over all n <= 16 buffers
+ * (bufs / sizes are HOST arrays of device pointers and element counts) into *total_norm (device),
+ * then every element times min(1, max_norm / (norm + 1e-6)).  One block sums the squares in fp64
+ * in a fixed order; a second launch scales. */
+int az_clip_grad_norm(float* const* bufs, const int64_t* sizes, int n, float max_norm,
+                      float* total_norm, void* stream);
+
 /* Per-row GNN evaluation tail: output_transform then the heads, i.e. gnn_utils.py:115 (in the
  * 1-row form of Connect4GNN.py:108-111, where the layers are the identity, gnn_utils.py:35-36)
  * followed by Connect4GNN.py:48-57 -- the batched predict_with_gnn after extract_features:
