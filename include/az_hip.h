@@ -341,7 +341,7 @@ typedef struct az_graph {
   const int* src_rowptr;  /* [V+1] reverse CSR by source */
   const int* src_edges;   /* [E] edge ids grouped by source (ascending within a source) */
   const int* dst_index;   /* [V] compact destination index, -1 when no in-edge */
-  int max_deg;            /* max in-degree (backward supports <= 256); only picks kernels: an
+  int max_deg;            /* max in-degree; only picks kernels, forward and backward: an
                              understated value is slower, never wrong (edges are not dropped) */
   int band;               /* max |src - dst| over the edges when the caller knows it, else 0.
                              Eval-mode layers on F = 64, H = 128 graphs with 0 < band <= 32 (the

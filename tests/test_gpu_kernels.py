@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import assert_close, golden, split_weights
+from gradcheck import check_dot_error  # noqa: F401  (shared with the backward tests)
 
 import os
 
@@ -32,14 +33,6 @@ def rel_err(a, b):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
     return np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
-
-
-def check_dot_error(got, ref, bound, tol=1e-6):
-    """fp32 dot products vs an fp64 reference: |err| <= tol * sum_k |a_k b_k| per element
-    (MI355X_MICROARCH.md: f32 MFMA error ~0.75-3.5e-7 of sum|a.b| up to K=4096)."""
-    err = np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64))
-    worst = (err / (np.asarray(bound, np.float64) + 1e-30)).max()
-    assert worst < tol, worst
 
 
 @pytest.mark.parametrize("M,N,K", [(1, 3136, 3136), (3, 37, 64), (8, 128, 6272), (64, 128, 3136),

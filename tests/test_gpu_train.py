@@ -9,7 +9,7 @@ The first term: as accurate as torch's own fp32 CPU gradient of the same restate
 10x.  The second term is the rounding floor of ANY fp32 evaluation of that gradient element:
 S_i is the sum of the absolute values of the terms that make up the element -- for every
 F.linear / F.conv2d y = x W^T + b of the float64 forward, |dy|^T |x| into W and sum_rows |dy|
-into b, dy being the loss gradient at y (abs_contributions below).  An fp32 sum of n terms is
+into b, dy being the loss gradient at y (abs_contributions, tests/gradcheck.py).  An fp32 sum of n terms is
 within a small multiple of u32 sum|t| of exact for the blocked / pairwise orders used here
 ((n-1) u32 sum|t| only for one long recursive chain, Higham 4.2), and a different but equally
 valid summation order (the HIP kernels') moves a result by the same amount.  This matters for gradients that are a near-total cancellation -- e.g. the attention
@@ -28,6 +28,8 @@ from conftest import golden, split_weights
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+from gradcheck import C_ROUND, MARGINS, U32, abs_contributions, check_grad, make_net  # noqa: E402,F401
+
 
 @pytest.fixture(scope="module")
 def lib():
@@ -38,76 +40,6 @@ def lib():
 def cu(a, dtype=None):
     t = torch.from_numpy(np.ascontiguousarray(a))
     return (t.to(dtype) if dtype is not None else t).cuda()
-
-
-U32 = 2.0 ** -24
-C_ROUND = 4
-MARGINS = {}     # name -> the C_ROUND this tensor needed (reported by test_report_margins)
-
-
-def check_grad(name, got, ref64, ref32, S=None):
-    got = np.asarray(got, np.float64).reshape(-1)
-    r = np.asarray(ref64, np.float64).reshape(-1)
-    r32 = np.asarray(ref32, np.float64).reshape(-1)
-    scale = max(np.abs(r).max(), 1e-30)
-    err = np.abs(got - r)
-    e_t32 = np.abs(r32 - r).max()
-    if S is None:
-        assert err.max() <= 10 * e_t32 + 1e-7 * scale, (name, err.max(), e_t32, scale)
-        return
-    S = np.asarray(S, np.float64).reshape(-1)
-    over = err - 10 * e_t32
-    need = float(np.max(np.where(over > 0, over / np.maximum(U32 * S, 1e-300), 0.0)))
-    MARGINS[name] = need
-    assert need <= C_ROUND, (name, err.max(), e_t32, need)
-
-
-def abs_contributions(run, P):
-    """S per parameter of the float64 restatement: |dy|^T |x| (weights) and sum |dy| (biases)
-    over every F.linear / F.conv2d that uses it, dy = d loss / d (that call's output).  `run`
-    builds the loss from P; the hooks fire during its backward."""
-    import torch.nn.functional as F
-    S = {k: torch.zeros_like(v.detach()) for k, v in P.items()}
-    name = {id(v): k for k, v in P.items()}
-    lin, conv = F.linear, F.conv2d
-
-    def track(y, x, w, b, kind, kw):
-        kw_, kb_ = name.get(id(w)), (name.get(id(b)) if b is not None else None)
-        if not y.requires_grad or (kw_ is None and kb_ is None):
-            return
-        xa = x.detach().abs()
-
-        def hook(dy):
-            d = dy.detach().abs()
-            if kind == "linear":
-                d2, x2 = d.reshape(-1, d.shape[-1]), xa.reshape(-1, xa.shape[-1])
-                if kw_:
-                    S[kw_] += d2.T @ x2
-                if kb_:
-                    S[kb_] += d2.sum(0)
-            else:
-                if kw_:
-                    S[kw_] += torch.nn.grad.conv2d_weight(xa, w.shape, d, **kw)
-                if kb_:
-                    S[kb_] += d.sum((0, 2, 3))
-        y.register_hook(hook)
-
-    def lin_t(x, w, b=None):
-        y = lin(x, w, b)
-        track(y, x, w, b, "linear", {})
-        return y
-
-    def conv_t(x, w, b=None, stride=1, padding=0, dilation=1, groups=1):
-        y = conv(x, w, b, stride, padding, dilation, groups)
-        track(y, x, w, b, "conv", dict(stride=stride, padding=padding, dilation=dilation,
-                                       groups=groups))
-        return y
-    F.linear, F.conv2d = lin_t, conv_t
-    try:
-        run(P).backward()
-    finally:
-        F.linear, F.conv2d = lin, conv
-    return {k: v.numpy() for k, v in S.items()}
 
 
 def ref_grads(fn, W, dtype):
@@ -121,21 +53,6 @@ def ref_grads(fn, W, dtype):
 def ref_contrib(fn, W):
     from oracle import torch_ref as R
     return abs_contributions(fn, R.params(W, torch.float64))
-
-
-def make_net(kind, W, G=None, dropout=0.0):
-    from types import SimpleNamespace
-    from azhip import nets
-    if kind == "c4":
-        game = SimpleNamespace(getBoardSize=lambda: (7, 7), getActionSize=lambda: 8)
-        net = nets.Connect4Net(game, {"dropout": dropout}, init=W)
-        F = 3136
-    else:
-        game = SimpleNamespace(getBoardSize=lambda: (3, 3), getActionSize=lambda: 10)
-        net = nets.TicTacToeNet(game, {}, init=W)
-        F = 128
-    gnn = nets.PolicyValueGNN(F, 2, init=G) if G is not None else None
-    return net, gnn
 
 
 def targets(B, A, seed):
