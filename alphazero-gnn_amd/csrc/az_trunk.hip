@@ -885,6 +885,47 @@ __global__ __launch_bounds__(1024) void splitk_heads_rowsw_kernel(
   });
 }
 
+// The split-K reduce of output_transform.0 fused with the composed heads (az_gemm.hip
+// composed_heads: wp / wv / bp / bv are rows of Wc / bc): a row's slabs are summed in slab order
+// from 0.f, then bias and activation -- splitk_reduce4_kernel's arithmetic, so the hidden rows'
+// bits are splitk_reduce's -- and feed heads_rowsw_body as heads_rowsw_kernel's x rows would;
+// `h` (may be null: the evaluator never reads the hidden rows) receives them.
+template <int AMAX, int S, int R>
+__global__ __launch_bounds__(1024) void splitk_act_heads_rowsw_kernel(
+    const float* __restrict__ slab, int B, int K, const float* __restrict__ bias, int act,
+    float* __restrict__ h, const float* __restrict__ wp, int A, const float* __restrict__ wv,
+    const float* __restrict__ bp, const float* __restrict__ bv, float* __restrict__ logp,
+    float* __restrict__ pi, float* __restrict__ v) {
+  const size_t plane = (size_t)B * K;
+  heads_rowsw_body<AMAX, R>(B, K, wp, A, wv, bp, bv, logp, pi, v,
+                            [&](int r0, int kc, bool kin, int k, f32x4 (&xs)[R], f32x4 (&ys)[R]) {
+    f32x4 sv[R][S];
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const size_t off = (size_t)min(r0 + i, B - 1) * K + kc;
+#pragma unroll
+      for (int q = 0; q < S; ++q) sv[i][q] = *reinterpret_cast<const f32x4*>(slab + q * plane + off);
+    }
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 bb = bias ? *reinterpret_cast<const f32x4*>(bias + kc) : z;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      f32x4 x;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float t = 0.f;
+#pragma unroll
+        for (int q = 0; q < S; ++q) t += sv[i][q][e];
+        if (bias) t += bb[e];
+        x[e] = kin ? apply_act(t, act) : 0.f;
+      }
+      if (h && kin && r0 + i < B) *reinterpret_cast<f32x4*>(h + (size_t)(r0 + i) * K + k) = x;
+      xs[i] = x;
+      ys[i] = x;
+    }
+  });
+}
+
 // Plain heads (x = hp rows, y = hv rows) with the same body: az_heads_fwd for B > 32, A <= 8.
 template <int AMAX, int R>
 __global__ __launch_bounds__(1024) void heads_rowsw_kernel(
@@ -1091,8 +1132,26 @@ int splitk_reduce_split(const az_gemm_desc* d, int splits, unsigned short* plane
                         hipStream_t s, bool write_c = true);
 bool gemm_p2_weights(const float* w, int n, int k, int ld);
 const float* conv2_frags(const float* w2, hipStream_t s);
+size_t composed_heads_scratch_bytes(int F, int A);
+const float* composed_heads(const float* w2, const float* b2, const float* wp, const float* bp,
+                            const float* wv, const float* bv, int F, int A, float* scratch,
+                            hipStream_t s);
 
 static size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// The composed-heads path (heads of y = x W^T + b without y: logits = x Wc^T + bc, az_gemm.hip
+// composed_heads) applies to y == NULL, A <= 8 and B above the 64 rows at which the GEMMs switch
+// to the fp16 split form -- a function of the call's shape alone, never of registration or of
+// the GEMM dispatch, so every variant of a call computes the same bits.  Tuning build:
+// AZ_NO_COMPOSED_HEADS keeps the heads from the GEMM's tiles (az_x3.h HeadsEpi) for A/B runs.
+constexpr int COMPOSED_HEADS_MIN_B = 65;
+static bool composed_heads_shape(int B, int A, bool want_y) {
+  static const bool off = tuning_env("AZ_NO_COMPOSED_HEADS") != nullptr;   // A/B experiments
+  return !off && !want_y && A >= 1 && A <= 8 && B >= COMPOSED_HEADS_MIN_B;
+}
+static size_t composed_heads_bytes(int F, int A) {   // the per-call Wc / bc and its partials
+  return align256(composed_heads_scratch_bytes(F, A));
+}
 
 // The B x F pre-split-A region at the END of a transform_heads / c4_eval workspace: two fp16
 // planes [2][B][F] and scales [2][B] (PreSplitA), written by the trunk for output_transform.0 and
@@ -1264,7 +1323,8 @@ namespace az {
 static int linear_heads_impl(const float* x, int B, int F, const float* w, const float* b,
                              const float* wp, const float* bp, int A, const float* wv,
                              const float* bv, float* y, float* logp, float* pi, float* v,
-                             void* ws, size_t ws_bytes, void* stream, const PreSplitA* pre) {
+                             void* ws, size_t ws_bytes, void* stream, const PreSplitA* pre,
+                             bool composed_ok = true) {
   AZ_REQUIRE(B >= 0 && F > 0 && F % 4 == 0 && A > 0 && A <= 32, AZ_EINVAL,
              "az_linear_heads_fwd: bad shape B=%d F=%d A=%d", B, F, A);
   if (B == 0) return AZ_OK;
@@ -1280,6 +1340,7 @@ static int linear_heads_impl(const float* x, int B, int F, const float* w, const
   // products to heads_tiles_finalize_kernel when it can (az_x3.h HeadsEpi); the other shapes
   // form y in a [B][F] scratch at the workspace's end
   const bool want_y = y != nullptr;
+  const size_t ws_total = ws_bytes;
   if (!want_y) {
     const size_t yb = align256((size_t)4 * B * F);
     AZ_REQUIRE(ws_bytes >= part_bytes + yb + 256, AZ_EINVAL,
@@ -1288,6 +1349,19 @@ static int linear_heads_impl(const float* x, int B, int F, const float* w, const
     y = reinterpret_cast<float*>(static_cast<char*>(ws) + ws_bytes);
   }
   float* part = static_cast<float*>(ws);
+  if (composed_ok && composed_heads_shape(B, A, want_y) &&
+      ws_total >= part_bytes + composed_heads_bytes(F, A)) {
+    // no GEMM: the heads' rows composed with W (cached per weight generation when every input
+    // is registered, else composed per call into the workspace after the heads' partials; a
+    // workspace without that room keeps the GEMM path), then the standard heads on the fp32 x
+    // rows (pre is not used)
+    float* scratch = reinterpret_cast<float*>(static_cast<char*>(ws) + part_bytes);
+    const float* wc = composed_heads(w, b, wp, bp, wv, bv, F, A, scratch, s);
+    AZ_REQUIRE(wc, AZ_EDEVICE, "az_linear_heads_fwd: composing the heads failed");
+    const float* bc = wc + (size_t)(A + 1) * F;
+    return az_heads_fwd(x, F, x, F, B, F, wc, bc, A, wc + (size_t)A * F, bc + A, logp, pi, v,
+                        part, part_bytes, stream);
+  }
   void* slabs = static_cast<char*>(ws) + part_bytes;
   int rc;
   // y = x W^T + b, its split-K reduction fused into the heads' first pass
@@ -1364,10 +1438,15 @@ static int linear_heads_impl(const float* x, int B, int F, const float* w, const
 }
 
 // az_transform_heads_fwd with x optionally pre-split (pre_x: the trunk wrote it into the
-// workspace's pre_region).  When output_transform.0 leaves split-K slabs and output_transform.2
-// takes the P2 path, the slabs' reduce also writes hidden's planes into pre_region
-// (splitk_reduce_split), so neither GEMM launches a split of its own; every output is bit-identical
-// to the unfused sequence (same planes, same products, same reduce arithmetic).
+// workspace's pre_region).  Composed heads (y == NULL, A <= 8, B > 64: what every evaluator
+// calls): output_transform.2 is never run -- when output_transform.0 leaves split-K slabs one
+// kernel reduces them and runs the heads composed with W2 on the rows
+// (splitk_act_heads_rowsw_kernel), else the GEMM writes the fp32 hidden rows and
+// linear_heads_impl runs the same heads on them.  Otherwise, when output_transform.0 leaves
+// split-K slabs and output_transform.2 takes the P2 path, the slabs' reduce also writes hidden's
+// planes into pre_region (splitk_reduce_split), so neither GEMM launches a split of its own.
+// Every output is bit-identical to the unfused sequence (same planes, same products, same reduce
+// arithmetic, same heads rows).
 static int transform_heads_impl(const float* x, int B, int F, const float* w0, const float* b0,
                                 const float* w2, const float* b2, const float* wp,
                                 const float* bp, int A, const float* wv, const float* bv,
@@ -1380,9 +1459,32 @@ static int transform_heads_impl(const float* x, int B, int F, const float* w0, c
   static const bool no_fuse = tuning_env("AZ_NO_PRESPLIT") != nullptr;   // A/B experiments
   // the region is reserved whenever the caller's pre_x lives in it (the same address: pre_region
   // depends only on ws, ws_bytes, B, F)
-  const PreRegion R = pre_x || (!no_fuse && gemm_p2_weights(w2, F, F, F))
-                          ? pre_region(ws, ws_bytes, B, F, part_bytes + (size_t)B * F * 8)
-                          : PreRegion{nullptr, nullptr, 0};
+  // composed heads (y == NULL, A <= 8, B > 64): output_transform.2 is folded into the heads'
+  // rows, so no region is reserved for its pre-split A and output_transform.0's slabs go
+  // straight to the fused reduce + heads kernel below
+  const int nch = (F + HEADS_KC - 1) / HEADS_KC;
+  bool composed = composed_heads_shape(B, A, y != nullptr) && w2 && b2 && wp && bp && wv && bv &&
+                  logp && v;
+  PreRegion R{nullptr, nullptr, 0};
+  // the per-call Wc / bc (unregistered weights) at the end of the workspace in front of the
+  // region, out of the GEMM's reach; a workspace without room for it keeps the tile path
+  float* wc_scratch = nullptr;
+  size_t wc_bytes = 0;
+  if (composed) {
+    if (pre_x) R = pre_region(ws, ws_bytes, B, F, part_bytes + (size_t)B * F * 8);
+    const size_t cb = composed_heads_bytes(F, A);
+    if (aligned16(ws) && ws_bytes >= part_bytes + R.bytes + cb + 256) {
+      wc_scratch = reinterpret_cast<float*>(static_cast<char*>(ws) +
+                                            (ws_bytes - R.bytes - cb) / 256 * 256);
+      wc_bytes = cb + 256;
+    } else {
+      composed = false;
+    }
+  }
+  if (!composed)
+    R = pre_x || (!no_fuse && gemm_p2_weights(w2, F, F, F))
+            ? pre_region(ws, ws_bytes, B, F, part_bytes + (size_t)B * F * 8)
+            : PreRegion{nullptr, nullptr, 0};
   AZ_REQUIRE(!pre_x || pre_x->planes == R.planes, AZ_EINVAL,
              "az_transform_heads_fwd: pre-split A outside the workspace's region");
   // hidden = relu(x W0^T + b0)   (output_transform.0 + ReLU); slabs after the heads' partials
@@ -1392,11 +1494,32 @@ static int transform_heads_impl(const float* x, int B, int F, const float* w0, c
   d.B = w0; d.ldb = F; d.b_kmajor = 1; d.bias = b0; d.act = AZ_ACT_RELU;
   d.C = hidden; d.ldc = F;
   d.ws = static_cast<char*>(ws) + part_bytes;
-  d.ws_bytes = ws_bytes - part_bytes - R.bytes;
+  d.ws_bytes = ws_bytes - part_bytes - R.bytes - wc_bytes;
   int S = 1, rc;
   if ((rc = gemm_f32_partial(&d, s, &S, pre_x))) return rc;
   PreSplitA pre_h{nullptr, nullptr};
-  if (S > 1) {
+  if (S > 1 && composed) {
+    // one launch sums the slabs (splitk_reduce's arithmetic) and runs the composed heads on the
+    // rows while they are in registers; the fp32 hidden rows leave only for a caller that gets
+    // them back.  Shapes the kernel does not take reduce the usual way and run the heads from
+    // the hidden rows below: the same bits
+    if (S <= 8 && nch <= 16 && aligned16(b0)) {
+      const float* wc = composed_heads(w2, b2, wp, bp, wv, bv, F, A, wc_scratch, s);
+      AZ_REQUIRE(wc, AZ_EDEVICE, "az_transform_heads_fwd: composing the heads failed");
+      const float* bc = wc + (size_t)(A + 1) * F;
+      const float* sl = static_cast<const float*>(d.ws);
+      float* h = hidden_scratch ? nullptr : hidden;
+      switch (S) {
+#define AZ_SKA(SS) case SS: hipLaunchKernelGGL((splitk_act_heads_rowsw_kernel<8, SS, 1>), dim3(B), \
+                                 dim3(64 * nch), 0, s, sl, B, F, b0, (int)AZ_ACT_RELU, h, wc, A,     \
+                                 wc + (size_t)A * F, bc, bc + A, logp, pi, v); break;
+        AZ_SKA(2) AZ_SKA(3) AZ_SKA(4) AZ_SKA(5) AZ_SKA(6) AZ_SKA(7) default: AZ_SKA(8)
+#undef AZ_SKA
+      }
+      return check_launch("splitk_act_heads_rowsw_kernel");
+    }
+    if ((rc = splitk_reduce(&d, S, s))) return rc;
+  } else if (S > 1) {
     // hidden_scratch (az_c4_eval_fwd's e->hidden): the fp32 hidden rows are skipped when
     // output_transform.2 certainly takes the reduce's planes -- gemm_p2_certain on the
     // descriptor linear_heads_impl builds (y NULL: its scratch y at the workspace's end)
@@ -1423,7 +1546,7 @@ static int transform_heads_impl(const float* x, int B, int F, const float* w0, c
   }
   // y = hidden W2^T + b2 (output_transform.2) and the heads
   return linear_heads_impl(hidden, B, F, w2, b2, wp, bp, A, wv, bv, y, logp, pi, v, ws,
-                           ws_bytes - R.bytes, stream, pre_h.planes ? &pre_h : nullptr);
+                           ws_bytes - R.bytes, stream, pre_h.planes ? &pre_h : nullptr, composed);
 }
 }  // namespace az
 
@@ -1547,8 +1670,10 @@ extern "C" int az_c4_eval_fwd(const az_c4_eval* e, const int8_t* boards, int B, 
   AZ_REQUIRE(aligned16(e->feat) && aligned16(e->hidden) && aligned16(e->ws), AZ_EINVAL,
              "az_c4_eval_fwd: scratch needs 16B alignment");
   const PreSplitA pre{R.planes, R.sc};
-  // y (the transform's output) is not an output of the evaluator: the heads come from the
-  // GEMM's tiles (az_x3.h HeadsEpi) wherever its shape allows
+  // y (the transform's output) is not an output of the evaluator: above 64 rows the heads are
+  // composed with output_transform.2 and run on output_transform.0's rows (one GEMM, then the
+  // fused reduce + heads); below, they come from the second GEMM's tiles (az_x3.h HeadsEpi)
+  // wherever its shape allows
   return transform_heads_impl(e->feat, B, 3136, e->ot0_w, e->ot0_b, e->ot2_w, e->ot2_b,
                               e->fc_policy_w, e->fc_policy_b, e->A, e->fc_value_w, e->fc_value_b,
                               e->hidden, nullptr, e->glogp, gpi, gv, e->ws, e->ws_bytes, stream,

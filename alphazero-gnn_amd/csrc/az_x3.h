@@ -166,6 +166,9 @@ struct PreSplitA {
 // B = 512 call than the split-K slabs and the heads pass that re-read them.
 // The stream-K form (gemm_x3_csk) writes one slot per wave instead: t = (64-column block) x
 // max_pieces + piece, and its finalize reads each tile's piece count from the plan.
+// The same linearity lets the evaluators skip the GEMM altogether (az_gemm.hip composed_heads:
+// the heads' rows times W, once per weight generation); this epilogue stays for the tuning
+// build's AZ_NO_COMPOSED_HEADS A/B runs and for workspaces without room for the composed rows.
 constexpr int HEADS_TILE_SLOTS = 9;
 struct HeadsEpi {
   const float* wp;   // fc_policy.weight [A][N]

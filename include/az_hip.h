@@ -169,16 +169,19 @@ typedef struct az_c4_eval {
 /* v != NULL: standard heads into pi [B][A] (may be NULL) and v [B];  gv != NULL: the GNN tail
  * into gpi / gv.  boards, pi, v, gpi, gv may be az_host_alloc memory.  With v == NULL (the
  * batched predict_with_gnn alone) and registered output_transform weights, the trunk writes
- * output_transform.0's operand already split for the fp16-form GEMM and that GEMM's split-K
- * reduce writes output_transform.2's, both into the last az_transform_heads_ws_bytes-sized
- * region of e->ws; the GNN tail runs as az_transform_heads_fwd with y = NULL (e->y is not
- * written for B > 8), so the outputs are bit-identical to az_c4_trunk_fwd +
- * az_transform_heads_fwd(y = NULL).  Both v and gv above 320 rows (predict_both): the same
+ * output_transform.0's operand already split for the fp16-form GEMM into the last
+ * az_transform_heads_ws_bytes-sized region of e->ws; the GNN tail runs as
+ * az_transform_heads_fwd with y = NULL (e->y is not written for B > 8), so the outputs are
+ * bit-identical to az_c4_trunk_fwd + az_transform_heads_fwd(y = NULL).  Above 64 rows that tail
+ * is ONE GEMM (output_transform.0) and one kernel that sums its split-K slabs, applies bias and
+ * ReLU and runs the heads composed with output_transform.2 on the rows (az_transform_heads_fwd
+ * below); up to 64 rows both GEMMs run.  Both v and gv above 320 rows (predict_both): the same
  * hand-off, and the trunk kernel that writes the split operand also forms the standard heads from
  * the rows in its LDS tile -- bit-identical to az_heads_fwd on feat.  e->feat and e->hidden are
- * scratch: above 64 rows, when output_transform.0 / .2 take the pre-split operands for certain
- * (registered weights, their planes cached) and nothing else reads the fp32 rows, those rows are
- * not written. */
+ * scratch: above 64 rows, when output_transform.0 takes the pre-split operand for certain
+ * (registered weights, their planes cached) and nothing else reads the fp32 feature rows, they
+ * are not written, and the hidden rows are not written when output_transform.0 leaves split-K
+ * slabs (the fused kernel keeps them in registers). */
 int az_c4_eval_fwd(const az_c4_eval* e, const int8_t* boards, int B, float* pi, float* v,
                    float* gpi, float* gv, void* stream);
 
@@ -307,12 +310,24 @@ int az_clip_grad_norm(float* const* bufs, const int64_t* sizes, int n, float max
  * dot products run in one pass (y is not re-read); results equal az_gemm_f32 + az_heads_fwd
  * bit for bit.  ws: >= az_heads_ws_bytes(B, F, A) rounded up to 256 B; az_transform_heads_ws_bytes
  * leaves room for the split-K slabs (a smaller workspace only limits the K split).
- * y may be NULL when only the heads are wanted (the evaluators): y is then never written -- on
- * the fp16-form split-K tiles (A <= 8, F % 32 == 0) every block folds its tile of y (+ b in its
- * first k split) into per-row dot products with wp / wv, heads_tiles_finalize_kernel sums them in
- * tile order (the heads are linear in y); other shapes form y in workspace scratch
- * (az_transform_heads_ws_bytes includes it).  Those results are the same function to fp32
- * rounding, not bit-identical to the y != NULL path (tests/test_gpu_kernels.py bounds it). */
+ * y may be NULL when only the heads are wanted (the evaluators): y is then never written.
+ * For A <= 8 and B > 64 it is never computed either: the heads are linear in y, so
+ *   logits = hidden Wc^T + bc,  Wc = [wp; wv] W2  ((A + 1) x F),  bc = [wp; wv] b2 + [bp; bv],
+ * with Wc / bc accumulated in fp64 and rounded once to fp32 (compose_heads_kernel).  They are
+ * cached per weight generation when W2, b2, wp, bp, wv and bv all lie in registered storage
+ * (az_weights_register; az_weights_changed covers the heads' weights too) and composed per call
+ * into the workspace otherwise -- the same kernels, so the same bits.  output_transform.2 then
+ * costs a 9-row product instead of a B-row GEMM: when output_transform.0 leaves split-K slabs,
+ * ONE kernel sums them in slab order, adds b0, applies ReLU (the plain reduce's arithmetic: the
+ * hidden rows keep their bits) and runs the heads on the rows in registers; when it leaves none
+ * (stream-K batches) the standard heads kernel reads the fp32 hidden rows.  The choice depends
+ * only on B, A, y == NULL and the workspace (az_transform_heads_ws_bytes holds the per-call
+ * Wc), never on registration.  Other shapes with y == NULL (B <= 64, A > 8) keep the earlier
+ * forms: on the fp16-form split-K tiles every block folds its tile of y into per-row dot products
+ * with wp / wv and heads_tiles_finalize_kernel sums them in tile order, else y is formed in
+ * workspace scratch (az_transform_heads_ws_bytes includes it).  y == NULL results are the same
+ * function to fp32 rounding, not bit-identical to the y != NULL path (tests/test_gpu_kernels.py
+ * and tests/test_gpu_composed_heads.py bound it). */
 size_t az_transform_heads_ws_bytes(int B, int F, int A);
 /* Its second half alone: y = x W^T + b, then the heads of y (same fusion, same workspace). */
 int az_linear_heads_fwd(const float* x, int B, int F, const float* w, const float* b,
@@ -531,7 +546,10 @@ int az_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
  * registered weights any way other than az_adam_f32 (which calls it) -- an optimizer step of its
  * own, loading a checkpoint, copying buffers -- must call it before the next GEMM on them.
  * A missed call is NOT a precision loss: above 64 rows the GEMM multiplies by the cached planes,
- * i.e. it returns the PREVIOUS weights' result.  (azhip/params.py FlatParams calls it for the
+ * i.e. it returns the PREVIOUS weights' result.  It covers more than GEMM operands: the heads
+ * composed with output_transform.2 (az_transform_heads_fwd with y = NULL) are cached the same
+ * way and depend on fc_policy / fc_value weights and biases and on output_transform.2's bias, so
+ * a write to any registered parameter needs the call.  (azhip/params.py FlatParams calls it for the
  * torch-side writes that bump the buffer's version counter -- in-place ops on the parameter
  * tensors -- and from copy_flat_ / weights_changed().  Writes through `.data`, and collectives
  * that write parameter views in place (dist.broadcast / all_reduce), do not bump it: such a
