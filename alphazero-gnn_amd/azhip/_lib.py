@@ -75,6 +75,11 @@ class C4Eval(ctypes.Structure):
                 ("ws_bytes", c_size_t), ("sync", c_void_p), ("err", c_void_p)]
 
 
+class C4nEval(ctypes.Structure):
+    """az_c4n_eval (include/az_hip.h): az_c4_eval's fields without sync / err, then n and F."""
+    _fields_ = C4Eval._fields_[:-2] + [("n", c_int), ("F", c_int)]
+
+
 class TttEval(ctypes.Structure):
     """az_ttt_eval (include/az_hip.h)."""
     _fields_ = ([(f"{l}_{k}", c_void_p) for l in ("conv1", "conv2", "conv3", "fc1", "fc2",
@@ -118,6 +123,14 @@ SIGNATURES = {
     "az_heads_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "az_c4_eval_fwd": (c_int, [ctypes.POINTER(C4Eval), c_void_p, c_int, c_void_p, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
+    "az_c4n_trunk_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
+    "az_c4n_trunk_heads_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "az_c4n_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "az_c4n_eval_fwd": (c_int, [ctypes.POINTER(C4nEval), c_void_p, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
     "az_ttt_trunk_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "az_ttt_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

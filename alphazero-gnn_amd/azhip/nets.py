@@ -83,13 +83,25 @@ class Connect4Net(_Net):
         W.sync()
         if self.n == 7:
             return ops.c4_trunk(b, W)
+        if self.n in ops.C4N_SIDES:      # one launch, bit-identical to features_eager
+            return ops.c4n_trunk(b, W)
+        return self.features_eager(b)
+
+    def features_eager(self, b):
+        """The two conv3x3_relu launches (any n)."""
+        W = self.params
+        W.sync()
         s = ops.conv3x3_relu(b, W["conv1.weight"], W["conv1.bias"], 1)
         s = ops.conv3x3_relu(s, W["conv2.weight"], W["conv2.bias"], 1)
         return s.view(s.shape[0], -1)
 
     def features_heads(self, b, pi=None, v=None):
-        """features(b) and heads of them -> (feat, logp, pi, v); one launch for small B on the
-        7x7 board (ops.c4_trunk_heads), bit-identical to the two calls."""
+        """features(b) and heads of them -> (feat, logp, pi, v), bit-identical to the two calls:
+        one launch for small B on the 7x7 board (ops.c4_trunk_heads) and at every B on 4x4, 5x5,
+        6x6 and 8x8 (ops.c4n_trunk_heads)."""
+        if self.n in ops.C4N_SIDES:
+            self.params.sync()
+            return ops.c4n_trunk_heads(b, self.params, pi=pi, v=v)
         if self.n != 7:
             f = self.features(b)
             return (f,) + self.heads(f, pi=pi, v=v)

@@ -184,6 +184,28 @@ class _TttDirectBatch(_DirectBatch):
         self.cap = cap
 
 
+class _C4nDirectBatch(_DirectBatch):
+    """_DirectBatch for the Connect4Net on 4x4, 5x5, 6x6 and 8x8 boards: ONE az_c4n_eval_fwd call
+    per batch, same host ring, same ownership tokens.  Without a GNN (the CNN-only wrapper) only
+    `both=False` batches exist and the descriptor carries no output_transform (and no
+    workspace)."""
+
+    def __init__(self, w, stream=None):
+        super().__init__(w, stream)
+        self.fn = _lib.lib().az_c4n_eval_fwd
+        self.fn_name = "az_c4n_eval_fwd"
+
+    def _grow(self, n):
+        w = self.w
+        cap = max(1024, 1 << (int(n) - 1).bit_length())
+        torch.cuda.synchronize(w.device)          # in-flight batches may use the old scratch
+        self.ev = ops.C4nEval(w.nnet.params, w.gnn.params if w.has_gnn else None, w.nnet.n,
+                              w.action_size, cap, w.device)
+        self.desc = self.ev.desc
+        self.ring = []        # entries still held by unread predictions keep their buffers
+        self.cap = cap
+
+
 class _PinnedRing:
     """Pinned host staging buffers reused round-robin (`depth` predictions in flight)."""
 
@@ -412,6 +434,9 @@ class _TttBatch1Direct(_Batch1Direct):
     call (4 launches for std, 6 for gnn / both; no in-kernel hand-over, so no timeout path).
     Same host layout, run() and run_rows() as the Connect4 evaluator."""
 
+    eval_class = ops.TttEval
+    fn_name = "az_ttt_eval_fwd"
+
     def __init__(self, w, kind, cap=1):
         dev = w.device
         A = w.action_size
@@ -422,7 +447,8 @@ class _TttBatch1Direct(_Batch1Direct):
         self.host = ops.HostBuffer(256 * cap + 4 * width * cap)
         self.h_in = self.host.view(0, torch.int8, (cap, w.board_x, w.board_y))
         self.h_out = self.host.view(256 * cap, torch.float32, (cap * width,))
-        self.ev = ops.TttEval(w.nnet.params, w.gnn.params if gnn else None, w.nnet.n, A, cap, dev)
+        self.ev = self.eval_class(w.nnet.params, w.gnn.params if gnn else None, w.nnet.n, A, cap,
+                                  dev)
         self.desc = self.ev.desc
         self.err_np = None
         o = self.h_out.numpy()
@@ -437,13 +463,21 @@ class _TttBatch1Direct(_Batch1Direct):
         self.views = views
         self.args = (ctypes.byref(self.desc), ctypes.c_void_p(self.h_in.data_ptr()))
         self.outs = tuple(None if v is None else ctypes.c_void_p(v.ctypes.data) for v in views)
-        self.fn = _lib.lib().az_ttt_eval_fwd
-        self.fn_name = "az_ttt_eval_fwd"
+        self.fn = getattr(_lib.lib(), self.fn_name)
         self.dev = dev
         self.stream = torch.cuda.current_stream(dev)
         self.sptr = ctypes.c_void_p(self.stream.cuda_stream)
         self.h_in_np = self.h_in.numpy()
         self.h_out_np = self.h_out.numpy()
+
+
+class _C4nBatch1Direct(_TttBatch1Direct):
+    """_Batch1Direct for the Connect4Net on 4x4, 5x5, 6x6 and 8x8 boards: up to `cap` boards as
+    ONE az_c4n_eval_fwd call (1 launch for std, 4 for gnn / both; no in-kernel hand-over, so no
+    timeout path).  Same host layout, run() and run_rows() as the 7x7 evaluator."""
+
+    eval_class = ops.C4nEval
+    fn_name = "az_c4n_eval_fwd"
 
 
 def _is_c4(w):
@@ -454,11 +488,16 @@ def _is_ttt(w):
     return isinstance(w.nnet, nets.TicTacToeNet) and 3 <= w.nnet.n <= 5
 
 
+def _is_c4n(w):
+    return isinstance(w.nnet, nets.Connect4Net) and w.nnet.n in ops.C4N_SIDES
+
+
 def _direct_ok(w):
     """az_c4_eval_fwd covers the 7x7 Connect4Net (+ PolicyValueGNN output_transform),
-    az_ttt_eval_fwd the TicTacToeNet on 3x3 .. 5x5 boards."""
+    az_c4n_eval_fwd the Connect4Net on 4x4, 5x5, 6x6 and 8x8 boards, az_ttt_eval_fwd the
+    TicTacToeNet on 3x3 .. 5x5 boards."""
     return (os.environ.get("AZ_B1_MODE", "direct") == "direct"
-            and (_is_c4(w) or _is_ttt(w))
+            and (_is_c4(w) or _is_c4n(w) or _is_ttt(w))
             and os.environ.get("AZ_NO_ZEROCOPY", "0") in ("", "0"))
 
 
@@ -514,7 +553,8 @@ class NetWrapper:
             if self.has_gnn:
                 self.gnn.eval()
             if _direct_ok(self):
-                cls = _TttBatch1Direct if _is_ttt(self) else _Batch1Direct
+                cls = (_TttBatch1Direct if _is_ttt(self) else
+                       _C4nBatch1Direct if _is_c4n(self) else _Batch1Direct)
                 g[kind] = cls(self, kind, cap=8 if kind == "both" else 1)
             else:
                 g[kind] = _Batch1Graph(self, kind)
@@ -559,12 +599,14 @@ class NetWrapper:
         each lane a stream, so one lane's batch can overlap the other's on the GPU); the caller
         orders the stream after any parameter update (play_episodes_engine does)."""
         self._sync_params()
-        if (self.has_gnn or _is_ttt(self)) and _direct_ok(self) and len(boards) > 0:
+        if (self.has_gnn or _is_ttt(self) or _is_c4n(self)) and _direct_ok(self) \
+                and len(boards) > 0:
             directs = self.__dict__.setdefault("_directs", {})
             key = None if stream is None else stream.cuda_stream
             d = directs.get(key)
             if d is None:
-                cls = _TttDirectBatch if _is_ttt(self) else _DirectBatch
+                cls = (_TttDirectBatch if _is_ttt(self) else
+                       _C4nDirectBatch if _is_c4n(self) else _DirectBatch)
                 d = directs[key] = cls(self, stream)
             self.nnet.eval()
             if self.has_gnn:
@@ -806,9 +848,10 @@ class GNNWrapperMixin:
     @property
     def batch_invariant_rows(self):
         """Largest batch whose predict_both rows are bit-identical to batch-1 calls: the 7x7
-        Connect4 evaluator (az_c4_eval_fwd) and the TicTacToe one (az_ttt_eval_fwd, n = 3..5)
-        compute every row of a batch of <= 8 with the batch-1 arithmetic
-        (tests/test_gpu_selfplay.py, tests/test_gpu_ttt_eval.py); 0 = no such guarantee."""
+        Connect4 evaluator (az_c4_eval_fwd), the one for 4x4, 5x5, 6x6 and 8x8 boards
+        (az_c4n_eval_fwd) and the TicTacToe one (az_ttt_eval_fwd, n = 3..5) compute every row of
+        a batch of <= 8 with the batch-1 arithmetic (tests/test_gpu_selfplay.py,
+        tests/test_gpu_c4n_eval.py, tests/test_gpu_ttt_eval.py); 0 = no such guarantee."""
         return 8 if _direct_ok(self) else 0
 
     def predict(self, board):
