@@ -3796,7 +3796,7 @@ struct WScaleEntry {
   float* pbuf[2];              // their row scales: a double buffer of its own, so a recompute
   int pcur;                    // of one kind never overwrites the other kind's live buffer
   long pgen;                   // generation planes[pcur] / pbuf[pcur] were split at
-  float* frags[2];             // conv2's weights in the trunk's MFMA fragment order (conv2_frags)
+  float* frags[2];             // conv2's fp16 fragment planes for the trunk (conv2_planes)
   int fcur;
   long fgen;
 };
@@ -4077,41 +4077,55 @@ __global__ __launch_bounds__(256) void heads_tiles_finalize_kernel(HeadsEpi he, 
   he.v[row] = tanhf(s[8] + he.bv[0]);
 }
 
-// The Connect4 trunk's conv2 weights ([64][32][3][3]) in the order its MFMA fragments use them
-// (az_trunk.hip c4_trunk_tile): frag[nt][q][lane][e] = w2[co][ci][tap] for step s = 4q + e
-// = tap * 8 + j, co = 16 nt + (lane & 15), ci = 8 (lane >> 4) + j.  A wave then loads its 72
-// weights as 18 coalesced 1-KB float4 loads instead of staging the 74 KB through LDS.
-__global__ __launch_bounds__(256) void c4_w2_frag_kernel(const float* __restrict__ w2,
-                                                         float* __restrict__ frag) {
-  const int i = blockIdx.x * 256 + threadIdx.x;       // 4 * 18 * 64 * 4 = 18,432 values
-  if (i >= 18432) return;
-  const int e = i & 3, lane = (i >> 2) & 63, q = (i >> 8) % 18, nt = i / (18 * 256);
-  const int st = 4 * q + e, tap = st >> 3, j = st & 7;
-  const int co = 16 * nt + (lane & 15), ci = 8 * (lane >> 4) + j;
-  frag[i] = w2[co * 288 + ci * 9 + tap];
+// The Connect4 trunk's conv2 weights ([64][32][3][3]) as the fp16 planes of its MFMA B fragments
+// (az_trunk.hip c4_trunk_tile), made once per weight generation instead of by every wave of every
+// block: wave nt (block nt) gathers each lane's 72 weights -- step s = tap * 8 + j takes
+// w2[co][ci][tap], co = 16 nt + (lane & 15), ci = 8 (lane >> 4) + j -- and runs w2_planes itself,
+// so the planes are bit for bit what the trunk would compute.  Layout: 16-B unit
+// [(nt * 18 + t) * 64 + lane] = tap t's high plane, [(nt * 18 + 9 + t) * 64 + lane] its low plane
+// (18 coalesced 1-KB loads per wave), then float [W2P_UNITS * 4 + nt * 64 + lane] = the lane's
+// channel's 1 / scale.
+constexpr int W2P_UNITS = 4 * 18 * 64;
+constexpr int W2P_FLOATS = W2P_UNITS * 4 + 4 * 64;
+__global__ __launch_bounds__(64) void c4_w2_planes_kernel(const float* __restrict__ w2,
+                                                          float* __restrict__ out) {
+  const int nt = blockIdx.x, lane = threadIdx.x;
+  const int co = 16 * nt + (lane & 15), h = lane >> 4;
+  float breg[72];
+#pragma unroll
+  for (int st = 0; st < 72; ++st) breg[st] = w2[co * 288 + (8 * h + (st & 7)) * 9 + (st >> 3)];
+  bf16x8 bh[9], bl[9];
+  const float iw = w2_planes(breg, bh, bl);
+  u32x4* const u = reinterpret_cast<u32x4*>(out);
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    u[(nt * 18 + t) * 64 + lane] = __builtin_bit_cast(u32x4, bh[t]);
+    u[(nt * 18 + 9 + t) * 64 + lane] = __builtin_bit_cast(u32x4, bl[t]);
+  }
+  out[W2P_UNITS * 4 + nt * 64 + lane] = iw;
 }
 
-// conv2_frags: the fragment-ordered copy of registered conv2 weights, cached per weight
-// generation like w_planes (double buffer, the recompute synchronises its stream before
-// publishing); nullptr for unregistered weights or when memory is short (the trunk then stages
-// the weights through LDS itself: the same values, the same bits).
-const float* conv2_frags(const float* w2, hipStream_t s) {
+// conv2_planes: the fragment planes of registered conv2 weights, cached per weight generation
+// like w_planes (double buffer, the recompute synchronises its stream before publishing);
+// nullptr for unregistered weights or when memory is short (the trunk then stages the weights
+// through LDS and splits them itself: the same planes, the same bits).
+const float* conv2_planes(const float* w2, hipStream_t s) {
   if (!weights_registered(w2, 64, 288, 288)) return nullptr;
   const long gen = g_wgen.load();
   std::lock_guard<std::mutex> lk(g_wmu);
   WScaleEntry* e = wcache_entry(w2, 64, 288, 288);
   if (!e) return nullptr;
   if (!e->frags[0]) {
-    if (hipMalloc(&e->frags[0], (size_t)2 * 18432 * sizeof(float)) != hipSuccess) {
+    if (hipMalloc(&e->frags[0], (size_t)2 * W2P_FLOATS * sizeof(float)) != hipSuccess) {
       e->frags[0] = nullptr;
       return nullptr;
     }
-    e->frags[1] = e->frags[0] + 18432;
+    e->frags[1] = e->frags[0] + W2P_FLOATS;
     e->fgen = 0;
   }
   if (e->fgen == gen) return e->frags[e->fcur];
   const int nxt = e->fcur ^ 1;
-  hipLaunchKernelGGL(c4_w2_frag_kernel, dim3(72), dim3(256), 0, s, w2, e->frags[nxt]);
+  hipLaunchKernelGGL(c4_w2_planes_kernel, dim3(4), dim3(64), 0, s, w2, e->frags[nxt]);
   if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
   e->fcur = nxt;
   e->fgen = gen;

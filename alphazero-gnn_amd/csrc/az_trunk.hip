@@ -23,8 +23,8 @@ namespace az {
 
 // LDS the kernel hands to c4_trunk_tile: (unregistered weights only) conv2's weights while they
 // are read into registers, then (NB <= 4) the NB*3136-float output staging tile, or (NB > 4, no
-// staging) conv1's output.  REGW (registered weights: the fragment-ordered copy is loaded straight
-// into registers) drops the 74 KB staging room, so NB <= 3 fits two blocks per CU.
+// staging) conv1's output.  REGW (registered weights: the cached fragment planes are loaded
+// straight into registers) drops the 74 KB staging room, so NB <= 3 fits two blocks per CU.
 //
 // Round 5 ran two blocks per CU and got WRONG rows, nondeterministically, in blocks sharing a CU.
 // Round 6 found the cause (tools/trunk_selfcheck_probe.py, profiles/r06/trunk_packed_fp32/):
@@ -39,18 +39,40 @@ namespace az {
 __device__ unsigned* g_trunk_chk;   // residency experiment log (az_debug_trunk_chk)
 #endif
 
+#ifdef AZ_TRUNK_STAMPS
+// timing-experiment library only (tools/trunk_stamp_probe.py): lane 0 of every wave of a trunk
+// block records s_memrealtime (100 MHz) at fixed points -- [block][8 waves][8]: 0 body start,
+// 1 prologue loads landed (first barrier), 2 conv2's weight split done (in-kernel split only),
+// 3 conv1's arithmetic done, 4 conv1's planes stored (barrier), 5 conv2 done, 6 rows staged
+// (barrier), 7 rows / planes written
+__device__ unsigned long long* g_trunk_stamps;
+#define AZ_TSTAMP(k)                                                                       \
+  do {                                                                                     \
+    const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                        \
+    if (g_trunk_stamps && (threadIdx.x & 63) == 0)                                         \
+      g_trunk_stamps[((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + (k)] = t_;        \
+  } while (0)
+#else
+#define AZ_TSTAMP(k)
+#endif
+
 template <int NB, bool REGW>
 constexpr int trunk_union_floats() {
   constexpr int after = NB <= 4 ? NB * 3136 : NB * C1_FLOATS_PER_BOARD;
   return REGW || after >= W2S_FLOATS ? after : W2S_FLOATS;
 }
 
-// occupancy asked of the compiler (waves per SIMD): two 8-wave blocks per CU where their LDS fits
-// (REGW, NB <= 3: <= 76 KB per block), else no constraint
+// Waves per block: 8, or (W4: registered weights, one board per block) 4 with wave = 16-channel
+// column tile taking every row tile.  A 4-wave block asks for each cached plane fragment once
+// (with 8 waves, waves w and w + 4 issue the same 18 1-KB loads) and four of them share a CU,
+// which pays above two 8-wave blocks per CU (B > 512 on 256 CUs; c4_trunk_launch's model).
+template <bool W4>
+constexpr int trunk_waves() { return W4 ? 4 : 8; }
+
+// occupancy asked of the compiler (waves per SIMD): at most 128 VGPRs where several blocks fit a
+// CU (REGW, NB <= 3: <= 76 KB of LDS per block), else no constraint
 template <int NB, bool REGW>
 constexpr int trunk_waves_per_eu() { return REGW && NB <= 3 ? 4 : 1; }
-template <int NB, bool REGW>
-constexpr int trunk_blocks_per_cu() { return REGW && NB <= 3 ? 2 : 1; }
 
 // The standard heads (Connect4Net.py:48-57: log_softmax(feat wp^T + bp), tanh(feat wv^T + bv)) of
 // the block's feature rows, for predict_both batches whose trunk stages its rows in LDS.
@@ -154,7 +176,7 @@ __device__ __forceinline__ void trunk_rows_heads(const float* ob, int nb, int b0
   }
 }
 
-// The trunk of one 512-thread block (boards blockIdx.x*NB ...).  `un` is LDS of
+// The trunk of one block of 512 (W4: 256) threads (boards blockIdx.x*NB ...).  `un` is LDS of
 // trunk_union_floats<NB, REGW>() floats: conv2's weights are staged there with coalesced float4 loads
 // (each lane then reads its 72 fragments from LDS -- one pass over the 74 KB per block instead of
 // 72 scattered 4-byte loads per lane in all 8 waves), and with NB <= 4 the feature rows are then
@@ -162,11 +184,14 @@ __device__ __forceinline__ void trunk_rows_heads(const float* ob, int nb, int b0
 // apl / asc (NB <= 4 only; may be null): the feature rows also leave as the P2 GEMM's A operand
 // for output_transform.0 (PreSplitA: two fp16 planes in the p2_chunk layout and scales [2][B], the bits
 // h3_split_rows_kernel would make of feat), so that GEMM needs no split launch of its own.
-// REGW: w2f (non-null) is conv2's weights already in fragment order (az_gemm.hip conv2_frags,
-// cached per weight generation): each lane loads its 72 weights as 18 coalesced float4 loads,
-// issued first, and the LDS staging of w2 (its bank-conflicted scalar stores and reads, a barrier)
-// is skipped; the registers hold the same values, so the bits are the same.  !REGW: w2f unused.
-template <int NB, bool HEADS = false, bool REGW = false>
+// REGW: w2f (non-null) is conv2's weights already split into the fp16 planes of the MFMA B
+// fragments (az_gemm.hip conv2_planes, cached per weight generation, made by w2_planes itself):
+// each lane loads its 9 high and 9 low fragments as 18 coalesced 16-byte loads and its channel's
+// 1 / scale; the LDS staging of w2 (its bank-conflicted scalar stores and reads, a barrier) and
+// the per-wave split are skipped; the registers hold the same values, so the bits are the same.
+// !REGW: w2f unused.  W4 (REGW, NB = 1): 4 waves, each taking all four row tiles of its column
+// tile -- every tile's MFMA chain keeps its tap order and its own accumulator, so the same bits.
+template <int NB, bool HEADS = false, bool REGW = false, bool W4 = false>
 __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards, int B,
                                               const float* __restrict__ w1,
                                               const float* __restrict__ b1,
@@ -178,6 +203,8 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
                                               const float* __restrict__ w2f = nullptr,
                                               const TrunkHeads* hd = nullptr) {
   static_assert(!HEADS || NB <= 4, "HEADS: the rows staged in LDS");
+  static_assert(!W4 || (REGW && NB == 1 && !HEADS),
+                "4 waves: the cached planes, one board per block, no heads (8 waves there)");
   float* const ob = un;
   constexpr int P = 49, PP = 81, CI = 32;
   constexpr int NT = TTILES[NB];          // 16-row tiles (az_trunk_rows.h order)
@@ -185,13 +212,14 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
   // float4 rows (the MFMA layout puts 16 channels 49 floats apart on consecutive lanes, so
   // direct stores scatter 4-byte writes); NB = 8 lacks the LDS for it
   constexpr bool STAGE = NB <= 4;
+  constexpr int NW = trunk_waves<W4>(), T = 64 * NW;   // waves, threads of the block
   __shared__ float bd[NB * PP + 1];
   // conv1's output planes (az_trunk_split.h): own LDS when the output is staged (NB <= 4), else
   // in `un` once conv2's weights have moved to registers
   __shared__ __attribute__((aligned(16))) float c1s[STAGE ? NB * C1_FLOATS_PER_BOARD : 4];
   float* const c1 = STAGE ? c1s : un;
   __shared__ float w1s[CI * 9 + CI + 1];   // conv1 weights, bias, pad: one round trip, then LDS
-  __shared__ float c1wmax[NB][8];          // each board's largest conv1 value, per wave
+  __shared__ float c1wmax[NB][NW];         // each board's largest conv1 value, per wave
   __shared__ float c1inv[NB];              // ... its planes' 1 / scale
   const int tid = threadIdx.x;
   const int b0 = blockIdx.x * NB;
@@ -201,71 +229,77 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
   const int h = lane >> 4, c16 = lane & 15;
   const int co = nt * 16 + c16;
   const uint16_t* const rows = trunk_rows<NB>();
-  // Every global load of the prologue is issued before the first one is waited for (conv2's
-  // 9 float4 per thread, the boards, conv1's weights, the bias), then the LDS stores: as a
-  // load -> store loop each iteration waited for its own round trip (11 in a row).
-  // conv2's weights -> LDS (row co = 288 floats = 72 float4, so no float4 crosses a row), or
-  // straight into the fragment registers from the fragment-ordered copy
-  constexpr int NW2 = 64 * 72 / 512;
-  f32x4v wst[NW2];
-  float breg[72];   // step s = tap * 8 + j takes channel ci = 8h + j of tap (lane group h)
-  if constexpr (REGW) {
-#pragma unroll
-    for (int q = 0; q < 18; ++q) {
-      const f32x4v v = reinterpret_cast<const f32x4v*>(w2f)[(nt * 18 + q) * 64 + lane];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) breg[4 * q + e] = v[e];
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < NW2; ++j) wst[j] = reinterpret_cast<const f32x4v*>(w2)[tid + 512 * j];
-  }
-  constexpr int NBD = (NB * PP + 511) / 512;
+  AZ_TSTAMP(0);
+  // Every global load of the prologue is issued before the first one is waited for, then the
+  // LDS stores: as a load -> store loop each iteration waited for its own round trip (11 in a
+  // row).  The boards, conv1's weights and the biases go first: vector loads return in order, so
+  // conv1 waits only for them.  conv2's weights: (!REGW) 9 float4 per thread -> LDS (row co =
+  // 288 floats = 72 float4, so no float4 crosses a row); (REGW) the cached planes are loaded
+  // straight into bh / bl after conv1's arithmetic, below.
+  constexpr int NBD = (NB * PP + T - 1) / T;
   int8_t bdv[NBD];
   bool bdin[NBD];
 #pragma unroll
   for (int j = 0; j < NBD; ++j) {
-    const int i = tid + 512 * j;
+    const int i = tid + T * j;
     const int b = i / PP, pp = i % PP, px = pp / 9, py = pp % 9;
     bdin[j] = i < NB * PP && b < nb && px >= 1 && px <= 7 && py >= 1 && py <= 7;
     bdv[j] = boards[bdin[j] ? (size_t)(b0 + b) * P + (px - 1) * 7 + (py - 1) : (size_t)b0 * P];
   }
-  const float w1v = tid < CI * 9 ? w1[tid] : b1[min(tid - CI * 9, CI - 1)];
+  constexpr int NW1 = (CI * 9 + CI + T - 1) / T;
+  float w1v[NW1];
+#pragma unroll
+  for (int j = 0; j < NW1; ++j) {
+    const int i = tid + T * j;
+    w1v[j] = i < CI * 9 ? w1[i] : b1[min(i - CI * 9, CI - 1)];
+  }
   const float bias = b2[co];
+  constexpr int NW2 = REGW ? 1 : 64 * 72 / T;
+  f32x4v wst[NW2];
+  bf16x8 bh[9], bl[9];
+  float iw;
+  if constexpr (!REGW) {
+#pragma unroll
+    for (int j = 0; j < NW2; ++j) wst[j] = reinterpret_cast<const f32x4v*>(w2)[tid + T * j];
+  }
   __builtin_amdgcn_sched_barrier(0);   // no load sinks into the guarded stores below
   if constexpr (!REGW) {
 #pragma unroll
     for (int j = 0; j < NW2; ++j) {
-      const int i = tid + 512 * j;
+      const int i = tid + T * j;
       float* d = un + (i / 72) * W2S_STRIDE + (i % 72) * 4;
       d[0] = wst[j][0]; d[1] = wst[j][1]; d[2] = wst[j][2]; d[3] = wst[j][3];
     }
   }
 #pragma unroll
   for (int j = 0; j < NBD; ++j)   // unguarded (past-the-end lanes hit bd's pad slot): a guarded
-    bd[min(tid + 512 * j, NB * PP)] = bdin[j] ? (float)bdv[j] : 0.f;   // use sinks the load
-  w1s[min(tid, CI * 9 + CI)] = w1v;     // unguarded: lanes past the 320 weights hit the pad
+    bd[min(tid + T * j, NB * PP)] = bdin[j] ? (float)bdv[j] : 0.f;   // use sinks the load
+#pragma unroll
+  for (int j = 0; j < NW1; ++j)         // unguarded: lanes past the 320 weights hit the pad
+    w1s[min(tid + T * j, CI * 9 + CI)] = w1v[j];
   __syncthreads();
+  AZ_TSTAMP(1);
   if constexpr (!REGW) {
+    float breg[72];   // step s = tap * 8 + j takes channel ci = 8h + j of tap (lane group h)
 #pragma unroll
     for (int s = 0; s < 72; ++s) {
       const int tap = s >> 3, ci = 8 * h + (s & 7);
       breg[s] = un[co * W2S_STRIDE + ci * 9 + (tap / 3) * 3 + (tap % 3)];
     }
+    iw = w2_planes(breg, bh, bl);
   }
-  bf16x8 bh[9], bl[9];
-  const float iw = w2_planes(breg, bh, bl);
+  AZ_TSTAMP(2);
   if constexpr (!STAGE && !REGW) __syncthreads();   // conv1's output overwrites the weights in `un`
   // conv1: (board, padded position, channel octet) items, kept in registers until each board's
   // maximum (its plane scale) is known
-  constexpr int NI = NB * PP * 4, NIT = (NI + 511) / 512;
+  constexpr int NI = NB * PP * 4, NIT = (NI + T - 1) / T;
   float cv[NIT][8];
   float cm[NB];                            // this lane's maximum per board, then the wave's
 #pragma unroll
   for (int b = 0; b < NB; ++b) cm[b] = 0.f;
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
-    const int i = tid + 512 * it;
+    const int i = tid + T * it;
     if (i < NI) {
       const int b = i / (PP * 4), r = i - b * (PP * 4);
       conv1_octet(w1s, bd + b * PP, r >> 2, r & 3, cv[it]);
@@ -274,6 +308,21 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
       for (int q = 0; q < NB; ++q)
         if (q == b) cm[q] = fmaxf(cm[q], m);
     }
+  }
+  AZ_TSTAMP(3);
+  if constexpr (REGW) {
+    // the lane's 18 cached plane fragments and its channel's 1 / scale, issued here: conv1's
+    // fma chains are done (72 more live registers through them would spill), and the loads have
+    // the maximum's exchange, the split, the image stores and two barriers to land
+    __builtin_amdgcn_sched_barrier(0);
+    const u32x4* const pu = reinterpret_cast<const u32x4*>(w2f) + nt * 18 * 64 + lane;
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      bh[t] = __builtin_bit_cast(bf16x8, pu[t * 64]);
+      bl[t] = __builtin_bit_cast(bf16x8, pu[(9 + t) * 64]);
+    }
+    iw = w2f[4 * 18 * 64 * 4 + nt * 64 + lane];
+    __builtin_amdgcn_sched_barrier(0);
   }
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
@@ -284,12 +333,12 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
   __syncthreads();
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
-    const int i = tid + 512 * it;
+    const int i = tid + T * it;
     if (i < NI) {
       const int b = i / (PP * 4), r = i - b * (PP * 4);
       float mx = c1wmax[b][0];
 #pragma unroll
-      for (int w = 1; w < 8; ++w) mx = fmaxf(mx, c1wmax[b][w]);
+      for (int w = 1; w < NW; ++w) mx = fmaxf(mx, c1wmax[b][w]);
       float inv;
       const float sa = h3_scale(mx, H3_TA, &inv);
       c1_store(c1 + b * C1_FLOATS_PER_BOARD, r >> 2, r & 3, cv[it], sa);
@@ -297,6 +346,7 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
     }
   }
   __syncthreads();
+  AZ_TSTAMP(4);
 #ifdef AZ_TRUNK_SELFCHECK
   // residency experiment: every thread re-derives conv1 item i (conv1_octet + the split, the
   // same arithmetic) and compares the two 16-B units of the image in LDS; mismatches are logged
@@ -309,7 +359,7 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
     asm volatile("" ::: "memory");
     conv1_octet(w1s, bd + b * PP, r >> 2, r & 3, v2);
     float mx = c1wmax[b][0];
-    for (int w = 1; w < 8; ++w) mx = fmaxf(mx, c1wmax[b][w]);
+    for (int w = 1; w < NW; ++w) mx = fmaxf(mx, c1wmax[b][w]);
     float inv;
     const float sa = h3_scale(mx, H3_TA, &inv);
     u32x4 o[2];
@@ -340,8 +390,8 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
     }
   };
 #pragma unroll
-  for (int it = 0; it < NIT; ++it) c1_check(0, tid + 512 * it);       // own item
-  c1_check(1, (tid + 192) % (NIT * 512));                           // another wave's item
+  for (int it = 0; it < NIT; ++it) c1_check(0, tid + T * it);       // own item
+  c1_check(1, (tid + 192) % (NIT * T));                           // another wave's item
 #endif
 
   // the wave's row tiles go in pairs (mt, mt + 2) with their two MFMA chains interleaved: each
@@ -353,10 +403,10 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
   float bm[NB];
 #pragma unroll
   for (int b = 0; b < NB; ++b) bm[b] = 0.f;
-  auto store_tile = [&](int mt, const f32x4v& acc) {
+  auto store_tile = [&](const uint16_t (&er)[4], const f32x4v& acc) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const int e = rows[16 * mt + h * 4 + r];
+      const int e = er[r];
       const int b = (e & 0x7fff) / P, p = (e & 0x7fff) - P * ((e & 0x7fff) / P);
       if (!(e & 0x8000) && b < nb) {
         const float v = acc[r] * (c1inv[b] * iw) + bias;
@@ -372,8 +422,18 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
       }
     }
   };
-  for (int mt = mh; mt < NT; mt += 4) {
+  // (4 waves: mh = 0 and the wave takes both pairs of every group of four tiles in turn)
+  for (int mt0 = 0; mt0 < NT; mt0 += 4)
+  for (int mt = mt0 + mh; mt < min(mt0 + 2, NT); mt += NW / 4) {
     const int u0 = a_unit(mt), u1 = a_unit(mt + 2);
+    // the epilogue's row entries, all eight loads in flight under the MFMA chain (read where they
+    // are used, each was a round trip of its own: 8 in a row per pair, most of this phase's time)
+    uint16_t er0[4], er1[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      er0[r] = rows[16 * mt + h * 4 + r];
+      er1[r] = rows[16 * (mt + 2 < NT ? mt + 2 : mt) + h * 4 + r];
+    }
     f32x4v acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
@@ -383,13 +443,14 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
       acc0 = conv2_step(ah0, al0, bh[tap], bl[tap], acc0);
       acc1 = conv2_step(ah1, al1, bh[tap], bl[tap], acc1);
     }
-    store_tile(mt, acc0);
-    if (mt + 2 < NT) store_tile(mt + 2, acc1);
+    store_tile(er0, acc0);
+    if (mt + 2 < NT) store_tile(er1, acc1);
   }
+  AZ_TSTAMP(5);
   if constexpr (STAGE) {
     // each board's max feature, one per wave (max is exact: any order gives the value
     // h3_split_rows_kernel computes from feat)
-    __shared__ float wmax[NB][8];
+    __shared__ float wmax[NB][NW];
     if (apl) {
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
@@ -399,22 +460,23 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
       }
     }
     __syncthreads();
+    AZ_TSTAMP(6);
 #ifdef AZ_TRUNK_SELFCHECK
 #pragma unroll
-    for (int it = 0; it < NIT; ++it) c1_check(2, tid + 512 * it);     // the image at the end
+    for (int it = 0; it < NIT; ++it) c1_check(2, tid + T * it);     // the image at the end
 #endif
     // feat may be null when apl is not: the caller's GEMM then reads only the planes
     f32x4v* dst = feat ? reinterpret_cast<f32x4v*>(feat + (size_t)b0 * 3136) : nullptr;
     const f32x4v* src = reinterpret_cast<const f32x4v*>(ob);
     if (!apl) {
-      for (int i = tid; i < nb * 784; i += 512) dst[i] = src[i];
+      for (int i = tid; i < nb * 784; i += T) dst[i] = src[i];
       return;
     }
-    for (int ch = tid; ch < nb * 392; ch += 512) {     // 8-float chunks: fp32 row + two planes
+    for (int ch = tid; ch < nb * 392; ch += T) {     // 8-float chunks: fp32 row + two planes
       const int b = ch / 392, c = ch - b * 392;
       float mx = wmax[b][0];
 #pragma unroll
-      for (int w = 1; w < 8; ++w) mx = fmaxf(mx, wmax[b][w]);
+      for (int w = 1; w < NW; ++w) mx = fmaxf(mx, wmax[b][w]);
       float inv;
       const float sc = h3_scale(mx, H3_TA, &inv);
       const f32x4v lo = src[2 * ch], hi = src[2 * ch + 1];
@@ -431,6 +493,7 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
         asc[B + b0 + b] = inv;
       }
     }
+    AZ_TSTAMP(7);
     if constexpr (HEADS) trunk_rows_heads<NB>(ob, nb, b0, *hd);   // ob is final since the barrier
   }
 }
@@ -439,7 +502,7 @@ __device__ __forceinline__ void c4_trunk_tile(const int8_t* __restrict__ boards,
 #define AZ_TRUNK_LB(NB_, REGW_)                                                                  \
   __attribute__((amdgpu_flat_work_group_size(1, 512),                                            \
                  amdgpu_waves_per_eu(trunk_waves_per_eu<NB_, REGW_>())))
-template <int NB, bool REGW = false>
+template <int NB, bool REGW = false, bool W4 = false>
 __global__ AZ_TRUNK_LB(NB, REGW) void c4_trunk_kernel(const int8_t* __restrict__ boards, int B,
                                                       const float* __restrict__ w1,
                                                       const float* __restrict__ b1,
@@ -448,12 +511,12 @@ __global__ AZ_TRUNK_LB(NB, REGW) void c4_trunk_kernel(const int8_t* __restrict__
                                                       float* __restrict__ feat,
                                                       const float* __restrict__ w2f = nullptr) {
   __shared__ __attribute__((aligned(16))) float un[trunk_union_floats<NB, REGW>()];
-  c4_trunk_tile<NB, false, REGW>(boards, B, w1, b1, w2, b2, feat, un, nullptr, nullptr, w2f);
+  c4_trunk_tile<NB, false, REGW, W4>(boards, B, w1, b1, w2, b2, feat, un, nullptr, nullptr, w2f);
 }
 
 // c4_trunk_kernel that also writes feat's rows as output_transform.0's pre-split A (NB <= 4)
 // HEADS: also the standard heads of the rows (predict_both above the one-launch trunk + heads size)
-template <int NB, bool HEADS = false, bool REGW = false>
+template <int NB, bool HEADS = false, bool REGW = false, bool W4 = false>
 __global__ AZ_TRUNK_LB(NB, REGW) void c4_trunk_split_a_kernel(
     const int8_t* __restrict__ boards, int B, const float* __restrict__ w1,
     const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
@@ -461,7 +524,7 @@ __global__ AZ_TRUNK_LB(NB, REGW) void c4_trunk_split_a_kernel(
     const float* __restrict__ w2f = nullptr, TrunkHeads hd = {}) {
   static_assert(NB <= 4, "the A split reads the LDS staging tile");
   __shared__ __attribute__((aligned(16))) float un[trunk_union_floats<NB, REGW>()];
-  c4_trunk_tile<NB, HEADS, REGW>(boards, B, w1, b1, w2, b2, feat, un, apl, asc, w2f, &hd);
+  c4_trunk_tile<NB, HEADS, REGW, W4>(boards, B, w1, b1, w2, b2, feat, un, apl, asc, w2f, &hd);
 }
 
 // Generic 3x3 conv + ReLU, one thread per output (TicTacToe trunks: tiny, latency-bound).
@@ -977,7 +1040,7 @@ __global__ __launch_bounds__(512) void c4_trunk_heads_kernel(
 using namespace az;
 
 namespace az {
-const float* conv2_frags(const float* w2, hipStream_t s);   // az_gemm.hip
+const float* conv2_planes(const float* w2, hipStream_t s);   // az_gemm.hip
 
 // The Connect4 trunk launch (az_c4_trunk_fwd); apl / asc non-null: when the chosen NB stages its
 // output in LDS (NB <= 4: B <= 1,024 on 256 CUs) the rows also leave as output_transform.0's
@@ -990,8 +1053,9 @@ static int c4_trunk_launch(const int8_t* boards, int B, const float* conv1_w,
   static const char* env = tuning_env("AZ_TRUNK_NB");   // tuning experiments only
   // boards per block from a fitted time model (below; every NB is bit-identical); when the caller
   // wants output_transform.0's A pre-split (apl), NB > 4 pays the separate split pass (~3.8 ns
-  // per board).  Registered weights: B = 512 -> 2 (12.2 us), 1,024 -> 2, 1,576 -> 2 (28.7 us;
-  // 33.2 at one block per CU in round 5), 3,150 -> 3 (44.3 us; 62.7), 4,096 -> 3 (51.7 us; 68.2)
+  // per board).  Registered weights (profiles/trunk_planes/trunk_nb_sweep.txt): B = 512 -> 1
+  // (9.1 us), 1,024 -> 1 in the 4-wave form (14.3 us), 1,576 -> the same (20.2 us), 3,150 (34.5 us),
+  // 4,096 (41.0 us)
   static int cus = 0;
   if (cus <= 0) {
     int dev = 0, n = 0;
@@ -999,35 +1063,41 @@ static int c4_trunk_launch(const int8_t* boards, int B, const float* conv1_w,
            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
            n > 0) ? n : 256;
   }
-  // conv2's weights in fragment order when they are registered (cached per weight generation):
-  // the REGW kernels, whose smaller LDS puts two blocks on a CU for NB <= 3
+  // conv2's fp16 fragment planes when the weights are registered (cached per weight generation):
+  // the REGW kernels, whose smaller LDS puts two 8-wave blocks on a CU for NB <= 3
   static const bool no_frag = tuning_env("AZ_TRUNK_NO_W2F") != nullptr;   // A/B experiments
-  const float* w2f = B > 8 && !no_frag ? conv2_frags(conv2_w, s) : nullptr;
+  const float* w2f = B > 8 && !no_frag ? conv2_planes(conv2_w, s) : nullptr;
   const bool regw = w2f != nullptr;
   int nbk = 0;
+  bool w4 = false;   // the 4-wave NB = 1 form (registered weights)
   if (B > 8) {
     // t = a(NB) + b(NB) x k, k = ceil(blocks / CUs) blocks per CU.  Registered weights (REGW,
-    // two blocks per CU for NB <= 3): refitted to profiles/r06/trunk_nb_sweep.txt; unregistered
-    // (one block per CU, conv2 staged through LDS): the round-5 fit
-    static const float ra[9] = {0.f, 4.3f, 5.f, 7.3f, 2.5f, 1.5f, 0.f, 0.f, 0.5f};
-    static const float rb[9] = {0.f, 4.1f, 5.95f, 7.3f, 14.3f, 22.f, 26.f, 29.7f, 32.5f};
+    // two blocks per CU for NB <= 3): refitted to profiles/trunk_planes/trunk_nb_sweep.txt;
+    // unregistered (one block per CU, conv2 staged through LDS): the round-5 fit
+    static const float ra[9] = {0.f, 3.4f, 5.4f, 6.f, 4.f, 1.5f, 0.f, 0.f, 0.5f};
+    static const float rb[9] = {0.f, 2.86f, 4.64f, 6.f, 12.6f, 22.f, 26.f, 29.7f, 32.5f};
     static const float ua[9] = {0.f, 2.f, 2.6f, 3.7f, 3.5f, 3.f, 0.f, 0.f, 0.f};
     static const float ub[9] = {0.f, 7.6f, 10.8f, 11.8f, 15.5f, 22.f, 26.f, 30.5f, 33.f};
-    const float* ta = regw ? ra : ua;
-    const float* tb = regw ? rb : ub;
+    // with the standard heads riding along (predict_both) a block also loads the heads' 113 KB
+    // of weights once for its NB rows, which the sweep did not time: those launches keep the
+    // round-6 fit (profiles/r06/trunk_nb_sweep.txt: B = 1,576 -> 2, 3,150 -> 3) and 8 waves
+    static const float ha[9] = {0.f, 4.3f, 5.f, 7.3f, 2.5f, 1.5f, 0.f, 0.f, 0.5f};
+    static const float hb[9] = {0.f, 4.1f, 5.95f, 7.3f, 14.3f, 22.f, 26.f, 29.7f, 32.5f};
+    const float* ta = regw ? (heads ? ha : ra) : ua;
+    const float* tb = regw ? (heads ? hb : rb) : ub;
     float best = 0.f;
     for (int nb = 1; nb <= 8; ++nb) {
       const long k = ((long)(B + nb - 1) / nb + cus - 1) / cus;
       const float t = ta[nb] + (float)k * tb[nb] + (apl && nb > 4 ? 0.0038f * B : 0.f);
       if (nb == 1 || t < best) best = t, nbk = nb;
     }
+    // the 4-wave form, one board per block: a higher floor and a lower slope (5.1 + 2.24 k: it
+    // wins from three 8-wave rounds on, B > 512 on 256 CUs, and by 15-25 % from B = 1,576)
+    static const bool no_w4 = tuning_env("AZ_TRUNK_NO_W4") != nullptr;   // A/B experiments
+    if (regw && !heads && !no_w4 && 5.1f + 2.24f * (float)((B + cus - 1) / cus) < best)
+      nbk = 1, w4 = true;
   }
-  // the split-A form without heads (the batched predict_with_gnn) above one round of 256 blocks
-  // and up to two blocks per CU: one board per block measured 1.3 us faster per B = 512 step
-  // than the model's NB = 2 (97.5 vs 98.8 us, tools/gpu_r06_nb_sweep.sh; the kernels alone are
-  // within 0.3 us: profiles/r06/trunk_nb/)
-  if (regw && apl && asc && !heads && B > cus && B <= 2 * cus) nbk = 1;
-  if (env) nbk = atoi(env);
+  if (env) nbk = atoi(env), w4 = w4 && nbk == 1;
   const bool sa = apl && asc && nbk >= 1 && nbk <= 4;
   if (split) *split = sa;
   // the standard heads ride along when the rows are staged in LDS (the split-A kernel)
@@ -1042,18 +1112,20 @@ static int c4_trunk_launch(const int8_t* boards, int B, const float* conv1_w,
 #else
   constexpr size_t dyn = 0;
 #endif
-#define AZ_TRUNK_RW(NB_, RW_)                                                                    \
-  if (hk) hipLaunchKernelGGL((c4_trunk_split_a_kernel<NB_, true, RW_>),                          \
+#define AZ_TRUNK_RW(NB_, RW_, W4_)                                                               \
+  constexpr int TT = 64 * trunk_waves<W4_>();                                                    \
+  if (hk) hipLaunchKernelGGL((c4_trunk_split_a_kernel<NB_, true, RW_, false>),                   \
                              dim3((B + NB_ - 1) / NB_), dim3(512), dyn, s, boards, B, conv1_w,  \
                              conv1_b, conv2_w, conv2_b, feat_sa, apl, asc, w2f, *heads);         \
-  else if (sa) hipLaunchKernelGGL((c4_trunk_split_a_kernel<NB_, false, RW_>),                    \
-                                  dim3((B + NB_ - 1) / NB_), dim3(512), dyn, s, boards, B,      \
+  else if (sa) hipLaunchKernelGGL((c4_trunk_split_a_kernel<NB_, false, RW_, W4_>),               \
+                                  dim3((B + NB_ - 1) / NB_), dim3(TT), dyn, s, boards, B,       \
                                   conv1_w, conv1_b, conv2_w, conv2_b, feat_sa, apl, asc, w2f,   \
                                   TrunkHeads{});                                                 \
-  else hipLaunchKernelGGL((c4_trunk_kernel<NB_, RW_>), dim3((B + NB_ - 1) / NB_), dim3(512),    \
-                          dyn, s, boards, B, conv1_w, conv1_b, conv2_w, conv2_b, feat, w2f);
+  else hipLaunchKernelGGL((c4_trunk_kernel<NB_, RW_, W4_>), dim3((B + NB_ - 1) / NB_),          \
+                          dim3(TT), dyn, s, boards, B, conv1_w, conv1_b, conv2_w, conv2_b, feat, \
+                          w2f);
 #define AZ_TRUNK(NB_)                                                                            \
-  if (regw) { AZ_TRUNK_RW(NB_, true) } else { AZ_TRUNK_RW(NB_, false) }
+  if (regw) { AZ_TRUNK_RW(NB_, true, false) } else { AZ_TRUNK_RW(NB_, false, false) }
 #define AZ_TRUNK_BIG(NB_)                                                                        \
   if (regw) hipLaunchKernelGGL((c4_trunk_kernel<NB_, true>), dim3((B + NB_ - 1) / NB_),         \
                                dim3(512), dyn, s, boards, B, conv1_w, conv1_b, conv2_w, conv2_b, \
@@ -1072,7 +1144,8 @@ static int c4_trunk_launch(const int8_t* boards, int B, const float* conv1_w,
       hipLaunchKernelGGL(c4_trunk_split_kernel, dim3(B, 4), dim3(256), 0, s, boards, conv1_w,
                          conv1_b, conv2_w, conv2_b, feat);
       break;
-    default: AZ_TRUNK(1)
+    default:
+      if (regw && w4) { AZ_TRUNK_RW(1, true, true) } else { AZ_TRUNK(1) }
   }
 #undef AZ_TRUNK
 #undef AZ_TRUNK_RW
@@ -1080,6 +1153,12 @@ static int c4_trunk_launch(const int8_t* boards, int B, const float* conv1_w,
   return check_launch("c4_trunk_kernel");
 }
 }  // namespace az
+
+#ifdef AZ_TRUNK_STAMPS
+extern "C" int az_debug_trunk_stamps(void* buf) {   // timing-experiment library only
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_trunk_stamps), &buf, sizeof(buf)) == hipSuccess ? 0 : -1;
+}
+#endif
 
 #ifdef AZ_TRUNK_SELFCHECK
 extern "C" int az_debug_trunk_chk(void* log) {   // residency experiment library only
@@ -1131,7 +1210,7 @@ bool gemm_p2_certain(const az_gemm_desc* d, hipStream_t s);
 int splitk_reduce_split(const az_gemm_desc* d, int splits, unsigned short* planes, float* sc,
                         hipStream_t s, bool write_c = true);
 bool gemm_p2_weights(const float* w, int n, int k, int ld);
-const float* conv2_frags(const float* w2, hipStream_t s);
+const float* conv2_planes(const float* w2, hipStream_t s);
 size_t composed_heads_scratch_bytes(int F, int A);
 const float* composed_heads(const float* w2, const float* b2, const float* wp, const float* bp,
                             const float* wv, const float* bv, int F, int A, float* scratch,
