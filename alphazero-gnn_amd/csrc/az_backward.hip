@@ -6,9 +6,9 @@
 #include <algorithm>
 
 #include "az_common.h"
+#include "az_gemm.h"
 
 namespace az {
-int gemm_f32(const az_gemm_desc* d, hipStream_t s);
 
 // Forward-workspace views (az_gnn.hip carve()): what az_gnn_layer_fwd kept for us.
 struct FwdSaved {

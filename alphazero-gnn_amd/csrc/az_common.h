@@ -163,7 +163,7 @@ __device__ __forceinline__ float wave_max(float v) {
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
-// A/B-experiment switches (AZ_GEMM_CFG, AZ_SPLITK_HEADS_MODE, ...) are read only by the tuning
+// A/B-experiment switches (AZ_GEMM_RING, AZ_SPLITK_HEADS_MODE, ...) are read only by the tuning
 // build (-DAZ_TUNING -> libaz_hip_tuning.so, used by tools/ and the kernel-variant test): the
 // product library never consults the environment and runs its fixed, measured dispatch.
 #ifdef AZ_TUNING

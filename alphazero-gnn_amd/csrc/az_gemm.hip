@@ -14,108 +14,16 @@
 #include <string.h>
 
 #include <algorithm>
-#include <atomic>
 #include <mutex>
 #include <type_traits>
-#include <utility>
 #include <unordered_map>
-#include <vector>
+#include <utility>
 
-#include "az_common.h"
-#include "az_x3.h"
+#include "az_gemm.h"
 #include "az_heads.h"
 #include "az_trunk_split.h"
 
 namespace az {
-
-struct GemmArgs {
-  int M, N, K;
-  const float* A; int lda;
-  const float* A2; int lda2; int K0;
-  const int* a_rows;
-  const float* B; int ldb;
-  const int* b_rows;
-  const float* bias; int act;
-  const float* R; int ldr;
-  const float* G; int ldg;
-  float beta;
-  float* C; int ldc;
-  const int* c_rows;
-  float* C2; int ldc2;
-  // split-K: block (tile, s) covers k in [s*kc, min(K, (s+1)*kc)) and writes raw partial sums
-  // to slab[s][M][N]; splitk_reduce_kernel sums the slabs in s order (deterministic) and runs
-  // the epilogue.
-  int splits, kc;
-  float* slab;
-  int vec_epi;  // host-checked: N, every leading dimension % 4 == 0 and 16-B aligned C/C2/R/G,
-                // so whole float4 rows can leave through epilogue_store4
-  int ablate;   // timing experiments only (AZ_GEMM_ABLATE, glds2): 1 = no DMA after the first
-                // tile, 2 = no barrier in the k loop; results are then wrong
-  // gemm_x3 with A already split (x3_split_kernel): three bf16 planes [3][M][K] at apl
-  const unsigned short* apl;
-  size_t apl_plane;   // elements per plane (M * K)
-  // gemm_p3: W already split too, three bf16 planes [3][N][K] at bpl (row stride K)
-  const unsigned short* bpl;
-  size_t bpl_plane;   // elements per plane (N * K)
-  // gemm_x3 in its fp16 form (H3): per-row power-of-two scales of A ([2][M]: s, then 1/s) and of
-  // W ([2][N]), row_scale_kernel
-  const float* sa;
-  const float* sw;
-  // gemm_p3 HEADS: the heads' dot products per tile row instead of C / slabs (az_x3.h HeadsEpi)
-  HeadsEpi he;
-  int heads_done;   // host side: launch_x3 ran the HEADS form (no C, no slabs written)
-};
-
-__device__ __forceinline__ void epilogue_store(const GemmArgs& p, int row, int col, float acc) {
-  if (row >= p.M || col >= p.N) return;
-  float v = acc + (p.bias ? p.bias[col] : 0.f);
-  if (p.act == AZ_ACT_DRELU) {
-    v = p.G[(size_t)row * p.ldg + col] > 0.f ? v : 0.f;
-  } else {
-    v = apply_act(v, p.act);
-  }
-  if (p.C2) p.C2[(size_t)row * p.ldc2 + col] = v;
-  const int cr = p.c_rows ? p.c_rows[row] : row;
-  if (p.R) v = p.R[(size_t)cr * p.ldr + col] + (p.G ? p.G[(size_t)row * p.ldg + col] : 1.f) * v;
-  float* dst = p.C + (size_t)cr * p.ldc + col;
-  if (p.beta != 0.f) v += p.beta * *dst;
-  *dst = v;
-}
-
-// epilogue_store for 4 consecutive columns (col % 4 == 0, col + 4 <= N, p.vec_epi): one float4
-// load / store per operand instead of four scalar ones.
-__device__ __forceinline__ void epilogue_store4(const GemmArgs& p, int row, int col, f32x4 v) {
-  if (row >= p.M || col >= p.N) return;
-  if (p.bias) {
-    const f32x4 b = *reinterpret_cast<const f32x4*>(p.bias + col);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] += b[c];
-  }
-  if (p.act == AZ_ACT_DRELU) {
-    const f32x4 g = *reinterpret_cast<const f32x4*>(p.G + (size_t)row * p.ldg + col);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = g[c] > 0.f ? v[c] : 0.f;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = apply_act(v[c], p.act);
-  }
-  if (p.C2) *reinterpret_cast<f32x4*>(p.C2 + (size_t)row * p.ldc2 + col) = v;
-  const int cr = p.c_rows ? p.c_rows[row] : row;
-  if (p.R) {
-    const f32x4 r = *reinterpret_cast<const f32x4*>(p.R + (size_t)cr * p.ldr + col);
-    f32x4 g = {1.f, 1.f, 1.f, 1.f};
-    if (p.G) g = *reinterpret_cast<const f32x4*>(p.G + (size_t)row * p.ldg + col);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] = r[c] + g[c] * v[c];
-  }
-  f32x4* dst = reinterpret_cast<f32x4*>(p.C + (size_t)cr * p.ldc + col);
-  if (p.beta != 0.f) {
-    const f32x4 o = *dst;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] += p.beta * o[c];
-  }
-  *dst = v;
-}
 
 // Loaders.  Every per-thread row pointer is resolved ONCE before the K loop, each load in the
 // loop is unconditional (rows past M/N are clamped to row 0: they only feed outputs that are
@@ -247,21 +155,15 @@ __device__ __forceinline__ void tile_of(int bid, int mt_n, int nt_n, int& mt, in
 // around a ticket counter -- was measured 1.8x slower here: a tile's 5 slabs are 320 KB, far
 // above the few tens of KB where one block's serial combine beats a separate launch;
 // cdna_hip_programming.md §5 "In-launch split-K reduction".)
-// WAVE_LOCAL: only some of the block's waves run the epilogue (gemm_x3ws: the producer waves
-// have left), each in its own stage region, so the block barriers become wave-local LDS waits.
-template <int MF, int TI, int TJ, bool WAVE_LOCAL = false, class Acc>
+template <int MF, int TI, int TJ, class Acc>
 __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, Acc (&acc)[TI][TJ], int r0,
                                               int c0, int sp, float* stage = nullptr) {
   // Each wave stages through its own LDS region, so only the first wait needs the block (the k
   // loop's last LDS reads, other waves' included, must be done before the region is written);
   // the per-chunk waits are wave-local: a __syncthreads there is also a release fence that drains
   // every outstanding global store (s_waitcnt vmcnt(0)) -- twice per 32-column chunk, with every
-  // block of a one-round grid storing at once (MI355X, tools/gpu_p3_abl.sh: 15 of 41 us at
-  // M = 512, 158 of 594 at M = 8,192 were this epilogue)
-  auto sync_first = [] {
-    if constexpr (WAVE_LOCAL) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    else __syncthreads();
-  };
+  // block of a one-round grid storing at once (15 of 41 us at M = 512, 158 of 594 at M = 8,192
+  // were this epilogue)
   auto sync = [] { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); };
   constexpr int NACC = MF == 32 ? 16 : 4;
   constexpr int WM = TI * MF, WN = TJ * MF;
@@ -278,7 +180,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, Acc (&acc)[TI][
     // stores over 2-4 rows per instruction): each 32-column chunk of the wave tile is written
     // to LDS [WM][36] and read back as float4 rows, 8 lanes per 128-B row segment.
     constexpr int LD = 36, CH = 32 / MF;   // MFMA column tiles per 32-column chunk
-    sync_first();                           // the k loop's last LDS reads are done everywhere
+    __syncthreads();                        // the k loop's last LDS reads are done everywhere
 #pragma unroll
     for (int cc = 0; cc < WN / 32; ++cc) {
 #pragma unroll
@@ -683,12 +585,10 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_glds(GemmArgs p) {
                                                                        : nullptr);
 }
 
-// Multi-stage LDS-DMA tile: NBUF buffers, tile t+NBUF-1 is issued while tile t is consumed, so
-// NBUF-1 tiles of DMA are in flight across each barrier.  No __syncthreads() in the loop (its
-// fence would drain the DMAs, vmcnt(0)): a counted `s_waitcnt vmcnt(N)` retires exactly the
-// oldest tile, then a raw s_barrier publishes it to every wave (cdna_hip_programming.md §5,
-// "Pipelining across barriers").  The LDS image is [row][BK] with the 16-B chunk XOR-swizzled
-// by the row bits that would otherwise put a 16-lane ds_read_b128 group on one bank set.
+// Rings of LDS-DMA stages (gemm_f32_glds2 NB = 3, gemm_p3): later stages stay in flight across
+// each barrier.  No __syncthreads() in such a loop (its fence would drain the DMAs, vmcnt(0)): a
+// counted `s_waitcnt vmcnt(N)` retires exactly the oldest stage, then a raw s_barrier publishes
+// it to every wave (cdna_hip_programming.md §5, "Pipelining across barriers").
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -697,171 +597,32 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int BK>
-__device__ __forceinline__ int swz(int r) {
-  // chunks per row = BK/4; rows per 256-B bank row = 256 / (BK*4)
-  if constexpr (BK == 32) return (r >> 1) & 7;
-  else if constexpr (BK == 16) return (r >> 2) & 3;
-  else return (r >> 0) & 15;   // BK = 64
-}
-
-template <int BM, int BN, int BK, int NBUF, int WGM, int WGN>
-__global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_glds_pipe(GemmArgs p) {
-  constexpr int NT = 64 * WGM * WGN, NW = NT / 64;
-  constexpr int WM = BM / WGM, WN = BN / WGN;
-  constexpr int TI = WM / 32, TJ = WN / 32;
-  constexpr int CPR = BK / 4;                    // 16-B chunks per row
-  constexpr int RPP = 64 / CPR;                  // rows per 1-KB wave piece
-  constexpr int APC = BM / RPP / NW, BPC = BN / RPP / NW;
-  constexpr int DPT = APC + BPC;                 // DMAs per thread per tile
-  constexpr int TILE = (BM + BN) * BK;
-  static_assert(TI >= 1 && TJ >= 1 && APC >= 1 && BPC >= 1 && NBUF >= 2, "bad tile");
-  static_assert(DPT * (NBUF - 2) <= 63, "vmcnt range");
-  __shared__ __attribute__((aligned(1024))) float smem[NBUF * TILE];
-
-  const int mt_n = (p.M + BM - 1) / BM, nt_n = (p.N + BN - 1) / BN;
-  const int nwg = mt_n * nt_n * p.splits;
-  const int bid = xcd_swizzle(blockIdx.x, nwg);
-  const int mt = bid % mt_n, nt = (bid / mt_n) % nt_n, sp = bid / (mt_n * nt_n);
-  const int m0 = mt * BM, n0 = nt * BN;
-  const int kbeg = sp * p.kc, kend = min(p.K, kbeg + p.kc);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave / WGN, wn = wave % WGN;
-
-  const int lrow = lane / CPR, pch = lane % CPR;
-  const float* asrc[APC];
-  const float* bsrc[BPC];
-  int akq[APC], bkq[BPC];
-#pragma unroll
-  for (int q = 0; q < APC; ++q) {
-    const int r = (q * NW + wave) * RPP + lrow;
-    const int gr = m0 + r < p.M ? m0 + r : 0;
-    asrc[q] = p.A + (size_t)gr * p.lda;
-    akq[q] = (pch ^ swz<BK>(r)) * 4;
-  }
-#pragma unroll
-  for (int q = 0; q < BPC; ++q) {
-    const int r = (q * NW + wave) * RPP + lrow;
-    const int gr = n0 + r < p.N ? n0 + r : 0;
-    bsrc[q] = p.B + (size_t)gr * p.ldb;
-    bkq[q] = (pch ^ swz<BK>(r)) * 4;
-  }
-  auto issue = [&](int buf, int k0) {
-    float* As = smem + buf * TILE;
-    float* Bs = As + BM * BK;
-#pragma unroll
-    for (int q = 0; q < APC; ++q) {
-      const int k = k0 + akq[q];
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(asrc[q] + (k < p.K ? k : 0)),
-          (__attribute__((address_space(3))) void*)(As + (q * NW + wave) * RPP * BK), 16, 0, 0);
-    }
-#pragma unroll
-    for (int q = 0; q < BPC; ++q) {
-      const int k = k0 + bkq[q];
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(bsrc[q] + (k < p.K ? k : 0)),
-          (__attribute__((address_space(3))) void*)(Bs + (q * NW + wave) * RPP * BK), 16, 0, 0);
-    }
-  };
-
-  f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int nk = (kend - kbeg + BK - 1) / BK;
-#pragma unroll
-  for (int t = 0; t < NBUF - 1; ++t)
-    if (t < nk) issue(t, kbeg + t * BK);
-  for (int kt = 0; kt < nk; ++kt) {
-    // tiles issued so far: min(nk, kt + NBUF - 1); retire tile kt, keep the later ones flying
-    const int later = min(nk, kt + NBUF - 1) - kt - 1;
-    if constexpr (NBUF >= 4) {
-      if (later >= 2) wait_vm<DPT * 2>();
-      else if (later == 1) wait_vm<DPT>();
-      else wait_vm<0>();
-    } else if constexpr (NBUF == 3) {
-      if (later >= 1) wait_vm<DPT>();
-      else wait_vm<0>();
-    } else {
-      wait_vm<0>();
-    }
-    lds_barrier();
-    const int cur = kt % NBUF;
-    const int k0 = kbeg + kt * BK;
-    if (k0 + BK > kend) {                        // partial last tile: zero A's k >= kend
-      float* As = smem + cur * TILE;
-      for (int idx = threadIdx.x; idx < BM * CPR; idx += NT) {
-        const int r = idx / CPR, lc = idx % CPR;
-        if (k0 + lc * 4 >= kend)
-          *reinterpret_cast<f32x4*>(As + r * BK + ((lc ^ swz<BK>(r)) * 4)) =
-              f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      lds_barrier();
-    }
-    if (kt + NBUF - 1 < nk) issue((kt + NBUF - 1) % NBUF, kbeg + (kt + NBUF - 1) * BK);
-    const float* As = smem + cur * TILE;
-    const float* Bs = As + BM * BK;
-#pragma unroll
-    for (int g = 0; g < BK / 8; ++g) {
-      f32x4 a[TI], b[TJ];
-      const int lc = g * 2 + (lane >> 5);
-#pragma unroll
-      for (int i = 0; i < TI; ++i) {
-        const int r = wm * WM + i * 32 + (lane & 31);
-        a[i] = *reinterpret_cast<const f32x4*>(As + r * BK + ((lc ^ swz<BK>(r)) * 4));
-      }
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) {
-        const int r = wn * WN + j * 32 + (lane & 31);
-        b[j] = *reinterpret_cast<const f32x4*>(Bs + r * BK + ((lc ^ swz<BK>(r)) * 4));
-      }
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int j = 0; j < TJ; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][t], b[j][t], acc[i][j], 0, 0, 0);
-    }
-  }
-
-  tile_epilogue<32, TI, TJ>(p, acc, m0 + wm * WM, n0 + wn * WN, sp,
-                            (NW * WM * 36 <= (int)(sizeof(smem) / 4)) ? smem + wave * (WM * 36)
-                                                                       : nullptr);
-}
-
 // LDS-DMA tile, v2: the same LDS image and DMA schedule as gemm_f32_glds, but every wave reads
 // ALL of its fragments for the k-tile (16 ds_read_b128) before the first MFMA, so the LDS
 // latency of later fragment groups hides behind the MFMAs of earlier ones (the compiler counts
-// lgkmcnt down group by group) instead of draining once per group.  MF selects the MFMA shape:
-//   MF = 32: v_mfma_f32_32x32x2_f32, lane l holds A[row l&31][4 k of chunk 2g + (l>>5)]
-//   MF = 16: v_mfma_f32_16x16x4_f32, lane l holds A[row l&15][4 k of chunk 4g + (l>>4)]
-// Element t of the 4-k fragment feeds MFMA t, so the k order inside a group is permuted (only
-// the fp32 summation order changes).  The 16x16 shape is the lower-energy one per FLOP
+// lgkmcnt down group by group) instead of draining once per group.  The MFMA is
+// v_mfma_f32_16x16x4_f32: lane l holds A[row l&15][4 k of chunk 4g + (l>>4)], and element t of
+// the 4-k fragment feeds MFMA t, so the k order inside a group is permuted (only the fp32
+// summation order changes).  The 16x16 shape is the lower-energy one per FLOP
 // (cdna_hip_programming.md §5.4 rule 28: the chip holds a higher clock on it).
 //
-// NB = 3 (IL = false only): a three-buffer LDS ring.  Tile kt + 2 is issued right after the
-// barrier that retires tile kt, so each DMA has two k-tiles of MFMA time to land instead of
-// one, and the wait before a tile is a counted vmcnt (the next tile's pieces stay in flight);
-// one barrier per k-tile.  256x128: 144 KB of LDS, one block per CU.
-template <int BM, int BN, int WGM, int WGN, int MF, bool IL, int NB = 2, bool ST = false>
+// NB = 3: a three-buffer LDS ring.  Tile kt + 2 is issued right after the barrier that retires
+// tile kt, so each DMA has two k-tiles of MFMA time to land instead of one, and the wait before
+// a tile is a counted vmcnt (the next tile's pieces stay in flight); one barrier per k-tile.
+// 256x128: 144 KB of LDS, one block per CU.
+template <int BM, int BN, int WGM, int WGN, int NB = 2, bool ST = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_glds2(GemmArgs p) {
-  static_assert(NB == 2 || (NB == 3 && !IL), "three-buffer ring without interleaved issue");
+  static_assert(NB == 2 || NB == 3, "two buffers or the three-buffer ring");
   static_assert(!ST || NB == 3, "the stagger needs the three-buffer ring");
-  constexpr int BK = 32;
+  constexpr int BK = 32, MF = 16;
   constexpr int NT = 64 * WGM * WGN, NW = NT / 64;
   constexpr int WM = BM / WGM, WN = BN / WGN;
   constexpr int TI = WM / MF, TJ = WN / MF;
-  constexpr int NG = MF == 32 ? BK / 8 : BK / 16;     // fragment groups per k-tile
-  constexpr int LSH = MF == 32 ? 5 : 4;                // lane >> LSH = chunk within a group
+  constexpr int NG = BK / 16;                          // fragment groups per k-tile
+  constexpr int LSH = 4;                               // lane >> LSH = chunk within a group
   constexpr int APC = BM / 8 / NW, BPC = BN / 8 / NW;
-  using acc_t = typename std::conditional<MF == 32, f32x16, f32x4>::type;
-  constexpr int NACC = MF == 32 ? 16 : 4;
+  using acc_t = f32x4;
+  constexpr int NACC = 4;
   static_assert(TI >= 1 && TJ >= 1 && APC >= 1 && BPC >= 1, "bad tile");
   __shared__ __attribute__((aligned(1024))) float smem[NB * (BM + BN) * BK];
 
@@ -908,23 +669,6 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_glds2(GemmArgs p) {
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)(bsrc[q] + (k < p.K ? k : 0)),
           (__attribute__((address_space(3))) void*)(Bs + (q * NW + wave) * 8 * BK), 16, 0, 0);
-    }
-  };
-  // one 1-KB DMA piece: q < APC is A piece q, else B piece q - APC
-  auto issue_piece = [&](int buf, int k0, int q) {
-    float* As = smem + buf * (BM + BN) * BK;
-    float* Bs = As + BM * BK;
-    if (q < APC) {
-      const int k = k0 + akq[q];
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(asrc[q] + (k < p.K ? k : 0)),
-          (__attribute__((address_space(3))) void*)(As + (q * NW + wave) * 8 * BK), 16, 0, 0);
-    } else {
-      const int qb = q - APC;
-      const int k = k0 + bkq[qb];
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(bsrc[qb] + (k < p.K ? k : 0)),
-          (__attribute__((address_space(3))) void*)(Bs + (qb * NW + wave) * 8 * BK), 16, 0, 0);
     }
   };
   auto zero_tail = [&](int buf, int k0) {
@@ -985,14 +729,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_glds2(GemmArgs p) {
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
-        for (int j = 0; j < TJ; ++j) {
-          if constexpr (MF == 32)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][i][t], b[g][j][t], acc[i][j],
-                                                             0, 0, 0);
-          else
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g][i][t], b[g][j][t], acc[i][j],
-                                                             0, 0, 0);
-        }
+        for (int j = 0; j < TJ; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g][i][t], b[g][j][t], acc[i][j],
+                                                           0, 0, 0);
     };
     if (nk > 0) issue(0, kbeg);
     if (nk > 1) issue(1, kbeg + BK);
@@ -1074,7 +813,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_glds2(GemmArgs p) {
   for (int kt = 0; kt < nk; ++kt) {
     const int cur = kt & 1;
     const bool more = kt + 1 < nk && !(p.ablate & 1);
-    if (!IL && more) issue(cur ^ 1, kbeg + (kt + 1) * BK);
+    if (more) issue(cur ^ 1, kbeg + (kt + 1) * BK);
     const float* S = smem + cur * (BM + BN) * BK;
     f32x4 a[NG][TI], b[NG][TJ];
     auto read = [&](int g) {
@@ -1098,31 +837,13 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_glds2(GemmArgs p) {
 #pragma unroll
         for (int i = 0; i < TI; ++i)
 #pragma unroll
-          for (int j = 0; j < TJ; ++j) {
-            if constexpr (MF == 32)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[g][i][t], b[g][j][t], acc[i][j],
-                                                               0, 0, 0);
-            else
-              acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g][i][t], b[g][j][t], acc[i][j],
-                                                               0, 0, 0);
-          }
+          for (int j = 0; j < TJ; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[g][i][t], b[g][j][t], acc[i][j],
+                                                             0, 0, 0);
         if (t == 0 && g + 1 < NG) {
           __builtin_amdgcn_sched_barrier(0);
           read(g + 1);
           __builtin_amdgcn_sched_barrier(0);
-        }
-        if constexpr (IL) {
-          // IL: the next tile's DMA pieces are spread over the first half of the MFMA steps
-          // (one DMA issue stalls the wave for ~60-180 cycles; beside MFMAs it hides)
-          constexpr int STEPS = NG * 4 / 2, PER = (APC + BPC + STEPS - 1) / STEPS;
-          const int st = g * 4 + t;
-          if (st < STEPS && more) {
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int u = 0; u < PER; ++u)
-              if (st * PER + u < APC + BPC) issue_piece(cur ^ 1, kbeg + (kt + 1) * BK, st * PER + u);
-            __builtin_amdgcn_sched_barrier(0);
-          }
         }
       }
     if (more) {
@@ -1155,13 +876,7 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_f32_glds2(GemmArgs p) {
 // ds_write_b128 per plane); one barrier per 32-k tile.  LDS image per plane: [row][32 bf16]
 // (64 B rows), 16-B chunk c stored at c ^ ((row >> 2) & 3), which makes the MFMA operand reads
 // (lane: row lane & 31, chunk 2s + (lane >> 5)) conflict-free for every ds_read_b128 lane group.
-// ABL (tuning build only, timing ablations whose results are wrong by design): 1 = every tile's
-// loads from the split's first four tiles (L2-resident), 2 = no MFMA, 4 = no split (raw bits)
-// APL: A comes as three bf16 planes split once by x3_split_kernel (p.apl, row stride K, K % 32
-// == 0): the tile copies them into the LDS image without any VALU, only W is split here.
-// MF = 16 (tuning build): v_mfma_f32_16x16x32_bf16 blocks, one k step per 32-k tile (lane l
-// holds row l & 15, k chunk l >> 4), against two 32x32x16 steps for MF = 32.
-template <int BM, int BN, int WGM, int WGN, int MF = 32, int PL = 3>
+template <int BM, int BN, int WGM, int WGN, int PL = 3>
 constexpr int x3_smem_bytes() {
   constexpr int NW = WGM * WGN, WM = BM / WGM;
   constexpr int BUF = PL * (BM + BN) * 64, STAGE = NW * WM * 36 * 4;
@@ -1181,21 +896,19 @@ constexpr int x3_smem_bytes() {
 // ah*bl + al*bh + ah*bh on v_mfma_f32_32x32x16_f16 (two LDS planes instead of three, half the
 // MFMAs), and the accumulators multiplied back by 1 / (sa[row] sw[col]) (exact) before the
 // epilogue.
-template <int BM, int BN, int WGM, int WGN, bool MASK, int ABL = 0, bool APL = false, int MF = 32,
-          bool FLEX = false, bool H3 = false, bool HEADS = false>
+template <int BM, int BN, int WGM, int WGN, bool MASK, bool FLEX = false, bool H3 = false,
+          bool HEADS = false>
 __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int mt, int nt,
                                              int sp, int kbeg, int kend, int bma = BM) {
-  static_assert(!APL || !MASK, "pre-split A needs whole 32-k tiles");
-  static_assert(!H3 || (!APL && ABL == 0 && MF == 32), "H3: the product form only");
-  static_assert(!FLEX || (BM == 256 && BN == 128 && WGM == 4 && WGN == 2 && MF == 32 && !APL),
+  static_assert(!FLEX || (BM == 256 && BN == 128 && WGM == 4 && WGN == 2),
                 "FLEX reshapes the 256 x 128 8-wave tile");
-  constexpr int BK = 32;
+  constexpr int BK = 32, MF = 32;                // v_mfma_f32_32x32x16: two k steps per tile
   constexpr int NT = 64 * WGM * WGN;
   constexpr int WM = BM / WGM, WN = BN / WGN;
   constexpr int TI = WM / MF, TJ = WN / MF;
-  constexpr int NSTEP = MF == 32 ? 2 : 1;
-  using acc_t = typename std::conditional<MF == 32, f32x16, f32x4>::type;
-  constexpr int NACC = MF == 32 ? 16 : 4;
+  constexpr int NSTEP = 2;
+  using acc_t = f32x16;
+  constexpr int NACC = 16;
   constexpr int ASEG = BM * 4 / NT, BSEG = BN * 4 / NT, NSEG = ASEG + BSEG;
   static_assert(TI >= 1 && TJ >= 1 && ASEG >= 1 && BSEG >= 1 && (BM * 4) % NT == 0 &&
                 (BN * 4) % NT == 0, "bad x3 tile");
@@ -1232,25 +945,15 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int 
     sk[q] = c * 8;
   }
   struct Regs {
-    f32x4 f[NSEG][2];                 // fp32 segments (A's only when !APL)
-    u32x4 pa[APL ? ASEG : 1][3];      // A's three bf16 planes when APL
+    f32x4 f[NSEG][2];                 // fp32 segments
+    u32x4 pa[1][3];                   // never touched: without these 48 bytes the 128 x 128 fp16
+                                      // tiles get another register allocation (other machine code)
   };
   // every load is unconditional (k clamped in bounds); k >= kend is zeroed at the split
   auto gload = [&](Regs& ld, int k0) {
-    if constexpr ((ABL & 1) != 0) k0 = kbeg + (k0 - kbeg) % (4 * BK);
 #pragma unroll
     for (int q = 0; q < NSEG; ++q) {
       const int k = k0 + sk[q];
-      if constexpr (APL) {
-        if (q < ASEG) {
-          const int r = (threadIdx.x + q * NT) >> 2;
-          const size_t off = (size_t)min(m0 + r, p.M - 1) * p.K + (k < p.K ? k : 0);
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl)
-            ld.pa[q][pl] = *reinterpret_cast<const u32x4*>(p.apl + pl * p.apl_plane + off);
-          continue;
-        }
-      }
       ld.f[q][0] = *reinterpret_cast<const f32x4*>(src[q] + (k < p.K ? k : 0));
       ld.f[q][1] = *reinterpret_cast<const f32x4*>(src[q] + (k + 4 < p.K ? k + 4 : 0));
     }
@@ -1258,14 +961,6 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int 
   auto split_store = [&](const Regs& ld, int buf, int k0, int q, auto mask) {
     char* base = smem + buf * BUF;
     u32x4 o[3];
-    if constexpr (APL) {
-      if (q < ASEG) {
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          *reinterpret_cast<u32x4*>(base + pl * PLANE + soff[q]) = ld.pa[q][pl];
-        return;
-      }
-    }
     if constexpr (H3) {
       u32x4 o2[2];
       if constexpr (decltype(mask)::value) {
@@ -1283,13 +978,6 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int 
       const int k = k0 + sk[q];
       const f32x4 z = {0.f, 0.f, 0.f, 0.f};
       split3(k < kend ? ld.f[q][0] : z, k + 4 < kend ? ld.f[q][1] : z, o);
-    } else if constexpr ((ABL & 4) != 0) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        o[0][e] = __float_as_uint(ld.f[q][0][e]);
-        o[1][e] = __float_as_uint(ld.f[q][1][e]);
-        o[2][e] = o[0][e];
-      }
     } else {
       split3(ld.f[q][0], ld.f[q][1], o);
     }
@@ -1318,10 +1006,10 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int 
     boff[j] = row * 64;
     bkey[j] = (row >> 2) & 3;
   }
-  const int hk = MF == 32 ? lane >> 5 : lane >> 4;
+  const int hk = lane >> 5;
   struct Frags { bf16x8 a[PL][TI], b[PL][TJ]; };
   auto read = [&](Frags& f, const char* S, int s) {
-    const int c = MF == 32 ? 2 * s + hk : hk;
+    const int c = 2 * s + hk;
 #pragma unroll
     for (int pl = 0; pl < PL; ++pl) {
 #pragma unroll
@@ -1333,11 +1021,6 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int 
     }
   };
   auto mfma6 = [&](const Frags& f, int i, int j) {
-    if constexpr ((ABL & 2) != 0) {
-      acc[i][j][0] += __builtin_bit_cast(float, __builtin_bit_cast(u32x4, f.a[0][i])[0] ^
-                                                    __builtin_bit_cast(u32x4, f.b[0][j])[0]);
-      return;
-    }
     acc_t t = acc[i][j];
     if constexpr (H3) {
       // fp16 terms (h = plane 0, l = plane 1), the dropped al*bl smallest; smallest first
@@ -1346,20 +1029,13 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int 
       t = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, t, 0, 0, 0);
       t = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, t, 0, 0, 0);
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, t, 0, 0, 0);
-    } else if constexpr (MF == 32) {
+    } else {
       t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][i], f.b[2][j], t, 0, 0, 0);
       t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[2][i], f.b[0][j], t, 0, 0, 0);
       t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1][i], f.b[1][j], t, 0, 0, 0);
       t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][i], f.b[1][j], t, 0, 0, 0);
       t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[1][i], f.b[0][j], t, 0, 0, 0);
       acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[0][i], f.b[0][j], t, 0, 0, 0);
-    } else {
-      t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[0][i], f.b[2][j], t, 0, 0, 0);
-      t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[2][i], f.b[0][j], t, 0, 0, 0);
-      t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[1][i], f.b[1][j], t, 0, 0, 0);
-      t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[0][i], f.b[1][j], t, 0, 0, 0);
-      t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[1][i], f.b[0][j], t, 0, 0, 0);
-      acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.a[0][i], f.b[0][j], t, 0, 0, 0);
     }
   };
 
@@ -1368,24 +1044,11 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int 
   // split + LDS stores (its registers were loaded one tile earlier) pinned between them, so the
   // conversion VALU issues while earlier MFMAs run.  `nxt` holds tile kt + 1, `fut` receives
   // tile kt + 2; MASK zeroes k >= kend (only the last tile can be partial).
-  Frags fz;
-  if constexpr ((ABL & 8) != 0) read(fz, smem, 0);
   constexpr int NG = TI * TJ;
   auto body = [&](auto mask, int kt, const Regs& nxt, Regs& fut) {
     const char* S = smem + (kt & 1) * BUF;
-    if constexpr ((ABL & 8) == 0) gload(fut, kbeg + (kt + 2) * BK);
+    gload(fut, kbeg + (kt + 2) * BK);
     Frags f0, f1;
-    if constexpr ((ABL & 8) != 0) {          // MFMA-only ablation: no loads, split or LDS reads
-      f0 = fz;
-      f1 = fz;
-#pragma unroll
-      for (int g = 0; g < NSTEP * NG; ++g) {
-        if (g < NG) mfma6(f0, g / TJ, g % TJ);
-        else mfma6(f1, (g - NG) / TJ, (g - NG) % TJ);
-      }
-      __syncthreads();
-      return;
-    }
     read(f0, S, 0);
 #pragma unroll
     for (int g = 0; g < NSTEP * NG; ++g) {
@@ -1454,11 +1117,10 @@ __device__ __forceinline__ void gemm_x3_body(const GemmArgs& p, char* smem, int 
                             reinterpret_cast<float*>(smem) + wave * (WM * 36));
 }
 
-template <int BM, int BN, int WGM, int WGN, bool MASK, int ABL = 0, bool APL = false, int MF = 32,
-          bool H3 = false, bool HEADS = false>
+template <int BM, int BN, int WGM, int WGN, bool MASK, bool H3 = false, bool HEADS = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x3(GemmArgs p) {
-  __shared__ __attribute__((aligned(1024))) char smem[x3_smem_bytes<BM, BN, WGM, WGN, MF, H3 ? 2 : 3>()];
-  static_assert(!HEADS || x3_smem_bytes<BM, BN, WGM, WGN, MF, H3 ? 2 : 3>() >=
+  __shared__ __attribute__((aligned(1024))) char smem[x3_smem_bytes<BM, BN, WGM, WGN, H3 ? 2 : 3>()];
+  static_assert(!HEADS || x3_smem_bytes<BM, BN, WGM, WGN, H3 ? 2 : 3>() >=
                               (WGM * WGN * 64 * 36 + WGM * (WGN - 1) * 64 * HEADS_TILE_SLOTS) * 4,
                 "heads epilogue: stage + comb must fit");
   const int mt_n = (p.M + BM - 1) / BM, nt_n = (p.N + BN - 1) / BN;
@@ -1466,136 +1128,23 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_x3(GemmArgs p) {
   int mt, nt, sp;
   tile_of(xcd_swizzle(blockIdx.x, nwg), mt_n, nt_n, mt, nt, sp);
   const int kbeg = sp * p.kc, kend = min(p.K, kbeg + p.kc);
-  gemm_x3_body<BM, BN, WGM, WGN, MASK, ABL, APL, MF, false, H3, HEADS>(p, smem, mt, nt, sp, kbeg,
-                                                                       kend);
-}
-
-// Stream-K form of gemm_x3 for grids whose tile count does not fill the chip in whole rounds
-// (M ~ 600 .. 2,000 at N = 3,136: 100 .. 200 tiles of 256 x 128 on 256 CUs).  The tiles' k-steps
-// (KT 32-k steps per tile, tiles in (mt fastest, nt) order) are cut into B contiguous ranges of
-// equal cost, one per block: a block finishes the tail of one tile and starts the next.  A step
-// costs 2 units, or SkPlan::wt for the last, partial row of m-tiles (1 = half: an experiment in
-// which the waves of a tail tile whose rows all lie past M skipped their MFMAs -- measured
-// slower, r03m: a tail step costs a full step at one MFMA wave per SIMD, and the blocks given
-// more tail steps became the critical path; wt = 2 in the product).  A range that
-// covers a whole tile writes C through the fused epilogue; a piece of a tile writes its raw
-// partial sums to slab[piece] (piece = the block's index among the tile's blocks), and
-// streamk_fixup4_kernel sums a split tile's pieces in piece order (deterministic) and runs the
-// epilogue.
-struct SkPlan {
-  int mt_n, KT, wt;     // m-tiles, k-steps per tile, cost of a last-row step (1 or 2)
-  long C;               // total cost units
-  int B;                // blocks
-};
-
-// cost units before k-step k of tile t
-__host__ __device__ __forceinline__ long sk_unit(const SkPlan& q, long t, int k) {
-  const long full_rows_done = t / q.mt_n;            // the last-row tiles before t
-  const long before = (t - full_rows_done) * 2L * q.KT + full_rows_done * (long)q.wt * q.KT;
-  return before + (long)k * ((int)(t % q.mt_n) == q.mt_n - 1 ? q.wt : 2);
-}
-// the block that runs k-step k of tile t
-__host__ __device__ __forceinline__ int sk_block(const SkPlan& q, long t, int k) {
-  return (int)(sk_unit(q, t, k) * q.B / q.C);
-}
-// block b's first k-step (flattened t * KT + k): the first whose cost position u satisfies
-// u * B / C >= b, i.e. u >= ceil(b * C / B)
-__device__ __forceinline__ long sk_first(const SkPlan& q, int b) {
-  const long u = ((long)b * q.C + q.B - 1) / q.B;
-  const long G = (long)(q.mt_n - 1) * 2 * q.KT + (long)q.wt * q.KT;   // one n-tile column
-  const long g = u / G, r = u - g * G;
-  long mt, k;
-  if (r < (long)(q.mt_n - 1) * 2 * q.KT) {
-    mt = r / (2L * q.KT);
-    k = (r - mt * 2L * q.KT + 1) / 2;
-  } else {
-    mt = q.mt_n - 1;
-    k = (r - (long)(q.mt_n - 1) * 2 * q.KT + q.wt - 1) / q.wt;
-  }
-  return (g * q.mt_n + mt) * q.KT + k;       // k == KT rolls over to the next tile's step 0
-}
-
-template <int BM, int BN, int WGM, int WGN, bool MASK>
-__global__ __launch_bounds__(64 * WGM * WGN) void gemm_x3_sk(GemmArgs p, SkPlan q) {
-  __shared__ __attribute__((aligned(1024))) char smem[x3_smem_bytes<BM, BN, WGM, WGN>()];
-  const int b = xcd_swizzle(blockIdx.x, q.B);
-  const int KT = q.KT, mt_n = q.mt_n;
-  long i0 = sk_first(q, b);
-  const long i1 = b + 1 < q.B ? sk_first(q, b + 1) : (long)mt_n * ((p.N + BN - 1) / BN) * KT;
-  while (i0 < i1) {
-    const int t = (int)(i0 / KT);
-    const int k0 = (int)(i0 - (long)t * KT);
-    const int k1 = (int)min((long)KT, k0 + (i1 - i0));
-    GemmArgs g = p;
-    int sp = 0;
-    if (k0 == 0 && k1 == KT) {
-      g.splits = 1;                       // the whole tile: fused epilogue into C
-    } else {
-      g.splits = 2;                       // a piece: raw partials into slab[piece]
-      sp = b - sk_block(q, t, 0);
-    }
-    gemm_x3_body<BM, BN, WGM, WGN, MASK>(g, smem, t % mt_n, t / mt_n, sp, 32 * k0,
-                                         min(p.K, 32 * k1));
-    i0 += k1 - k0;
-    if (i0 < i1) __syncthreads();         // the next segment's prologue reuses the LDS
-  }
-}
-
-#ifdef AZ_TUNING   // round 3's stream-K (gemm_x3_sk, gemm_p3_sk): A/B runs only
-// Sums the pieces of every tile gemm_x3_sk / gemm_p3_sk split (slab[0 .. np), np = the tile's
-// block count) and runs the epilogue on them; whole tiles were written by their block.  float4
-// per lane.
-__global__ __launch_bounds__(256) void streamk_fixup4_kernel(GemmArgs p, int BM, int BN, SkPlan q) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  const int n4 = p.N >> 2;
-  if (idx >= (long)p.M * n4) return;
-  const int row = (int)(idx / n4), col = (int)(idx % n4) * 4;
-  const long t = (long)(col / BN) * q.mt_n + row / BM;
-  const int bf = sk_block(q, t, 0), bl = sk_block(q, t, q.KT - 1);
-  if (bf == bl) return;
-  const size_t plane = (size_t)p.M * p.N, off = (size_t)row * p.N + col;
-  f32x4 v = *reinterpret_cast<const f32x4*>(p.slab + off);
-  for (int s = 1; s <= bl - bf; ++s) {
-    const f32x4 u = *reinterpret_cast<const f32x4*>(p.slab + s * plane + off);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) v[c] += u[c];
-  }
-  epilogue_store4(p, row, col, v);
-}
-
-#endif
-
-// The stream-K plan for a BM x BN tile grid on B blocks (host); weighted: the last row of
-// m-tiles costs half when at most 128 of its rows are real (see gemm_x3_sk; not used).
-static SkPlan sk_plan(int M, int N, int K, int BM, int BN, int B, bool weighted) {
-  SkPlan q;
-  q.mt_n = (M + BM - 1) / BM;
-  q.KT = (K + 31) / 32;
-  const int rows_last = M - (q.mt_n - 1) * BM;
-  q.wt = weighted && rows_last < BM && rows_last <= BM / 2 ? 1 : 2;
-  const long nt_n = (N + BN - 1) / BN;
-  q.C = nt_n * ((long)(q.mt_n - 1) * 2 * q.KT + (long)q.wt * q.KT);
-  q.B = B;
-  return q;
-}
-// the most pieces any tile of plan q is cut into (slabs needed)
-static int sk_max_pieces(const SkPlan& q, int N, int BN) {
-  const long tiles = (long)q.mt_n * ((N + BN - 1) / BN);
-  int mx = 1;
-  for (long t = 0; t < tiles; ++t)
-    mx = std::max(mx, sk_block(q, t, q.KT - 1) - sk_block(q, t, 0) + 1);
-  return mx;
+  gemm_x3_body<BM, BN, WGM, WGN, MASK, false, H3, HEADS>(p, smem, mt, nt, sp, kbeg, kend);
 }
 
 // ---------------------------------------------------------------------------------------------
-// Cycled stream-K ("csk"): gemm_x3_sk with the tile order and the block -> XCD placement chosen
-// for L2 reuse, and a short tile for a mostly padded last m-row.
+// Cycled stream-K ("csk") form of gemm_x3 for grids whose tile count does not fill the chip in
+// whole rounds (M ~ 600 .. 2,000 at N = 3,136: 100 .. 200 tiles of 256 x 128 on 256 CUs): the
+// tiles' k-steps (KT 32-k steps per tile) are cut into contiguous ranges of equal length, one per
+// block, so a block finishes the tail of one tile and starts the next.  A range that covers a
+// whole tile writes C through the fused epilogue; a piece of a tile writes its raw partial sums
+// to a slab.  The tile order and the block -> XCD placement are chosen for L2 reuse, and a mostly
+// padded last m-row gets a short tile.
 //
-// gemm_x3_sk walks the whole (tile, k) sequence with B equal ranges, so the blocks that need the
-// same A panel (same m-tile) or W panel (same n-tile) at the same k run 16-36 k-steps apart: on
-// one XCD that is ~25 MB of other loads in between, far beyond its 4 MB L2, and every k-slab of
-// A and W is fetched again from the Infinity Cache by each of its consumers (980 MB per dispatch
-// at the self-play shapes against ~86 MB algorithmic, L2 hit 0.29; r03x).
+// Cutting the whole (tile, k) sequence into B equal ranges (plain stream-K) puts the blocks that
+// need the same A panel (same m-tile) or W panel (same n-tile) at the same k 16-36 k-steps
+// apart: on one XCD that is ~25 MB of other loads in between, far beyond its 4 MB L2, and every
+// k-slab of A and W is fetched again from the Infinity Cache by each of its consumers (980 MB per
+// dispatch at the self-play shapes against ~86 MB algorithmic, L2 hit 0.29; r03x).
 //
 // Here the tiles are grouped into CYCLES, macro tiles of am x an tiles (slot f = fm + am * fn
 // holds tile (cm * am + fm, cn * an + fn) of cycle (cm, cn)), and every cycle's am * an * KT
@@ -1605,7 +1154,7 @@ static int sk_max_pieces(const SkPlan& q, int N, int BN) {
 // hold a 2-D set of tiles (every cm, every cn), in which each A k-slab is read by the cycles
 // along n and each W k-slab by the cycles along m at the same k, out of that XCD's L2.
 // Measured (tools/csk_probe.py, profiles/r04a_csk.jsonl): M = 1,536 with am x an = 1 x 5 on 240
-// blocks runs 62 steps per block in 200 us, gemm_x3_sk 58 steps on 256 blocks in 203 us:
+// blocks runs 62 steps per block in 200 us, plain stream-K 58 steps on 256 blocks in 203 us:
 // 3.22 vs 3.49 us per step.
 //
 // A last m-row with at most 128 real rows runs 128 x 256 tiles instead of mostly padded
@@ -1645,21 +1194,20 @@ __device__ unsigned long long* g_p3_stamps;
 #endif
 // gemm_p3_body (below): the tile on operands already split into planes, LDS-DMA only
 template <int BM, int BN, int WGM, int WGN, bool H3 = false, bool FLEX = false, int NBUF = 2,
-          int ABL = 0, bool HEADS = false>
+          bool HEADS = false>
 __device__ __forceinline__ void gemm_p3_body(const GemmArgs& p, char* smem, int mt, int nt,
                                              int sp, int kbeg, int kend, int bma = BM);
 
 // P2: the fp16 form on pre-split planes (p.apl: A's two planes from h3_split_rows_kernel, p.bpl:
-// W's, cached per weight generation), every stage global -> LDS by LDS-DMA; same products in the
-// same order as the in-tile split, so the same bits.
-// RING (P2 only): the pre-split tile's LDS-DMA ring depth, 3 in the product (two stages in
-// flight: the whole-line stage fill then takes 0.60 us per stage against the MFMA's ~0.73)
-template <bool MASK, bool H3, bool P2 = false, bool HEADS = false, int RING = 3>
+// W's, cached per weight generation), every stage global -> LDS by LDS-DMA in a ring of three
+// (two stages in flight: the whole-line stage fill then takes 0.60 us per stage against the
+// MFMA's ~0.73); same products in the same order as the in-tile split, so the same bits.
+template <bool MASK, bool H3, bool P2 = false, bool HEADS = false>
 __global__ __launch_bounds__(512) void gemm_x3_csk(GemmArgs p, CskPlan q) {
   static_assert(!P2 || (H3 && !MASK), "P2: the fp16 form on whole 32-k tiles");
   static_assert(!HEADS || (H3 && !MASK), "HEADS: the fp16 form on whole 32-k tiles");
-  constexpr int SMEM = P2 ? p3_smem_bytes<256, 128, 4, 2, true, RING>()
-                          : x3_smem_bytes<256, 128, 4, 2, 32, H3 ? 2 : 3>();
+  constexpr int SMEM = P2 ? p3_smem_bytes<256, 128, 4, 2, true, 3>()
+                          : x3_smem_bytes<256, 128, 4, 2, H3 ? 2 : 3>();
   __shared__ __attribute__((aligned(1024))) char smem[SMEM];
   const int L = xcd_swizzle(blockIdx.x, q.B);
   int r, b, am, an, mt0, nt0, bma;
@@ -1702,11 +1250,11 @@ __global__ __launch_bounds__(512) void gemm_x3_csk(GemmArgs p, CskPlan q) {
     int mt_i = mt0 + (f - fn * am), bma_i = bma;   // opaque per segment: keeps the body's
     asm volatile("" : "+s"(mt_i), "+s"(bma_i));    // address setup in the loop (hoisted, it spills)
     if constexpr (P2)
-      gemm_p3_body<256, 128, 4, 2, true, true, RING, 0, HEADS>(g, smem, mt_i, nt0 + fn, sp,
-                                                              32 * k0, min(p.K, 32 * k1), bma_i);
+      gemm_p3_body<256, 128, 4, 2, true, true, 3, HEADS>(g, smem, mt_i, nt0 + fn, sp, 32 * k0,
+                                                        min(p.K, 32 * k1), bma_i);
     else
-      gemm_x3_body<256, 128, 4, 2, MASK, 0, false, 32, true, H3, HEADS>(
-          g, smem, mt_i, nt0 + fn, sp, 32 * k0, min(p.K, 32 * k1), bma_i);
+      gemm_x3_body<256, 128, 4, 2, MASK, true, H3, HEADS>(g, smem, mt_i, nt0 + fn, sp, 32 * k0,
+                                                         min(p.K, 32 * k1), bma_i);
     i0 += k1 - k0;
     if (i0 < i1) __syncthreads();         // the next segment's prologue reuses the LDS
   }
@@ -1902,9 +1450,7 @@ static bool csk_plan_cached(int M, int N, int K, int cus, double miss_cost, CskP
 // FLEX (the cycled stream-K tail): bma = 256 (256 x 128 tile) or 128 (128 x 256), as gemm_x3_body.
 // NBUF = 3: a three-stage ring (stage kt + 2 issued while stage kt computes), one barrier per
 // stage as with two; the fp16 256 x 128 ring is 3 x 48 KB.
-// ABL (tuning-build timing ablations, results wrong by design): 1 = no epilogue stores,
-// 2 = no MFMAs, 4 = no DMA (stale LDS)
-template <int BM, int BN, int WGM, int WGN, bool H3, bool FLEX, int NBUF, int ABL, bool HEADS>
+template <int BM, int BN, int WGM, int WGN, bool H3, bool FLEX, int NBUF, bool HEADS>
 __device__ __forceinline__ void gemm_p3_body(const GemmArgs& p, char* smem, int mt, int nt,
                                              int sp, int kbeg, int kend, int bma) {
   static_assert(NBUF == 2 || NBUF == 3, "p3 ring: 2 or 3 stages");
@@ -1945,7 +1491,6 @@ __device__ __forceinline__ void gemm_p3_body(const GemmArgs& p, char* smem, int 
     }
   }
   auto issue_one = [&](int buf, int k0, int q) {   // k0 % 32 == 0: step k0 / 32 at element 2 k0
-    if constexpr ((ABL & 4) != 0) return;
     __builtin_amdgcn_global_load_lds(
         (const __attribute__((address_space(1))) void*)(src[q] + 2 * k0),
         (__attribute__((address_space(3))) void*)(smem + buf * BUF + (q * NW + wave) * 1024),
@@ -1992,13 +1537,6 @@ __device__ __forceinline__ void gemm_p3_body(const GemmArgs& p, char* smem, int 
   };
   auto mfma6 = [&](const Frags& f, int i, int j) {
     f32x16 t = acc[i][j];
-    if constexpr ((ABL & 2) != 0) {       // keep the fragment reads live, no MFMA
-      acc[i][j][0] += __builtin_bit_cast(float, __builtin_bit_cast(u32x4, f.a[0][i])[0]) +
-                      __builtin_bit_cast(float, __builtin_bit_cast(u32x4, f.b[0][j])[0]) +
-                      __builtin_bit_cast(float, __builtin_bit_cast(u32x4, f.a[PL - 1][i])[1]) +
-                      __builtin_bit_cast(float, __builtin_bit_cast(u32x4, f.b[PL - 1][j])[1]);
-      return;
-    }
     if constexpr (H3) {
       const f16x8 ah = __builtin_bit_cast(f16x8, f.a[0][i]), al = __builtin_bit_cast(f16x8, f.a[PL - 1][i]);
       const f16x8 bh = __builtin_bit_cast(f16x8, f.b[0][j]), bl = __builtin_bit_cast(f16x8, f.b[PL - 1][j]);
@@ -2091,17 +1629,6 @@ __device__ __forceinline__ void gemm_p3_body(const GemmArgs& p, char* smem, int 
       }
     __syncthreads();           // the epilogue's staging reuses the stage buffers
   }
-  if constexpr ((ABL & 1) != 0) {        // no stores unless a sentinel appears (every
-    float t = 0.f;                         // accumulator stays live: no MFMA is dead code)
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int j = 0; j < TJ; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += acc[i][j][r];
-    if (t == 12345.f) p.C[0] = t;
-    return;
-  }
   if constexpr (HEADS) {
     static_assert(H3 && WN == 64 && TI == 2, "heads epilogue: the P2 tiles");
     float* f = reinterpret_cast<float*>(smem);
@@ -2121,8 +1648,7 @@ __device__ __forceinline__ void gemm_p3_body(const GemmArgs& p, char* smem, int 
 #endif
 }
 
-template <int BM, int BN, int WGM, int WGN, bool H3 = false, int NBUF = 2, int ABL = 0,
-          bool HEADS = false>
+template <int BM, int BN, int WGM, int WGN, bool H3 = false, int NBUF = 2, bool HEADS = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_p3(GemmArgs p) {
   __shared__ __attribute__((aligned(1024))) char smem[p3_smem_bytes<BM, BN, WGM, WGN, H3, NBUF>()];
   static_assert(!HEADS || p3_smem_bytes<BM, BN, WGM, WGN, H3, NBUF>() >=
@@ -2133,394 +1659,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_p3(GemmArgs p) {
   int mt, nt, sp;
   tile_of(xcd_swizzle(blockIdx.x, nwg), mt_n, nt_n, mt, nt, sp);
   const int kbeg = sp * p.kc, kend = min(p.K, kbeg + p.kc);
-  gemm_p3_body<BM, BN, WGM, WGN, H3, false, NBUF, ABL, HEADS>(p, smem, mt, nt, sp, kbeg, kend,
-                                                              BM);
+  gemm_p3_body<BM, BN, WGM, WGN, H3, false, NBUF, HEADS>(p, smem, mt, nt, sp, kbeg, kend, BM);
 }
-
-// gemm_x3 as a two-group ping-pong ("x3pp").  The timing ablations of gemm_x3 (tools/gemm_sweep.py
-// x3, tuning tiles 7-11) showed its MFMAs and its other work do not overlap: M = 4096 takes
-// 518 us, 219 us of it without any MFMA and ~200 us of MFMA alone; the loads are not the
-// bound (L2-resident loads: 503 us).  Both waves of a SIMD reach the same phase together after
-// every barrier.  Here the 8 waves (4 x 2, 64 x 64 each) form two groups of one wave per SIMD,
-// G0 = waves 0-3 and G1 = waves 4-7, and each 32-k tile t is two phases split by block
-// barriers:
-//   P1(t): G0 runs tile t's 48 MFMAs from fragments already in registers; G1 reads tile t's
-//          fragments, splits its share of tile t + 1 into LDS and issues its loads for t + 2;
-//   P2(t): G1 runs tile t's MFMAs; G0 reads tile t + 1's fragments, splits its share of tile
-//          t + 2 and issues its loads for t + 3.
-// So each SIMD's MFMA pipe alternates between its two waves while the other one does the LDS /
-// VALU / load work.  LDS: the planes of tiles t and t + 1 (the same double-buffered image as
-// gemm_x3); tile t + 2's shares overwrite tile t's buffer only after both groups have read it.
-// Same split and product order as gemm_x3.
-template <int BM, int BN, bool MASK>
-__global__ __launch_bounds__(512) void gemm_x3pp(GemmArgs p) {
-  constexpr int BK = 32, WGM = 4, WGN = 2, NT = 512;
-  constexpr int WM = BM / WGM, WN = BN / WGN, TI = WM / 32, TJ = WN / 32;
-  constexpr int ASEG = BM * 4 / NT, BSEG = BN * 4 / NT, NSEG = ASEG + BSEG;
-  static_assert(TI >= 1 && TJ >= 1 && ASEG >= 1 && BSEG >= 1 && (BM * 4) % NT == 0 &&
-                (BN * 4) % NT == 0, "bad x3pp tile");
-  constexpr int PLANE = (BM + BN) * 64, BUF = 3 * PLANE;
-  constexpr int STAGE = 8 * WM * 36 * 4;
-  constexpr int SMEM = 2 * BUF > STAGE ? 2 * BUF : STAGE;
-  __shared__ __attribute__((aligned(1024))) char smem[SMEM];
-
-  const int mt_n = (p.M + BM - 1) / BM, nt_n = (p.N + BN - 1) / BN;
-  const int nwg = mt_n * nt_n * p.splits;
-  const int bid = xcd_swizzle(blockIdx.x, nwg);
-  const int mt = bid % mt_n, nt = (bid / mt_n) % nt_n, sp = bid / (mt_n * nt_n);
-  const int m0 = mt * BM, n0 = nt * BN;
-  const int kbeg = sp * p.kc, kend = min(p.K, kbeg + p.kc);
-  const int nk = (kend - kbeg + BK - 1) / BK;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = wave / WGN, wn = wave % WGN;
-  const bool g1 = __builtin_amdgcn_readfirstlane(wave) >= 4;
-
-  const float* src[NSEG];
-  int soff[NSEG], sk[NSEG];
-#pragma unroll
-  for (int q = 0; q < NSEG; ++q) {
-    const bool isa = q < ASEG;
-    const int idx = threadIdx.x + (isa ? q : q - ASEG) * NT;
-    const int r = idx >> 2, c = idx & 3;
-    if (isa) {
-      const int gr = m0 + r < p.M ? m0 + r : 0;     // clamped rows feed outputs never stored
-      src[q] = p.A + (size_t)gr * p.lda;
-    } else {
-      const int gr = n0 + r < p.N ? n0 + r : 0;
-      src[q] = p.B + (size_t)gr * p.ldb;
-    }
-    const int row = isa ? r : BM + r;
-    soff[q] = row * 64 + ((c ^ ((row >> 2) & 3)) << 4);
-    sk[q] = c * 8;
-  }
-  f32x4 ld[NSEG][2];
-  auto gload = [&](int k0) {
-#pragma unroll
-    for (int q = 0; q < NSEG; ++q) {
-      const int k = k0 + sk[q];
-      ld[q][0] = *reinterpret_cast<const f32x4*>(src[q] + (k < p.K ? k : 0));
-      ld[q][1] = *reinterpret_cast<const f32x4*>(src[q] + (k + 4 < p.K ? k + 4 : 0));
-    }
-  };
-  // buffer indices are compile-time (B = 0 / 1) so the LDS addresses are a few per-lane bases
-  // plus immediate offsets, not a hoisted copy per buffer
-  auto split_store = [&](auto B, int k0) {
-    char* base = smem + decltype(B)::value * BUF;
-#pragma unroll
-    for (int q = 0; q < NSEG; ++q) {
-      u32x4 o[3];
-      if constexpr (MASK) {
-        const int k = k0 + sk[q];
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        split3(k < kend ? ld[q][0] : z, k + 4 < kend ? ld[q][1] : z, o);
-      } else {
-        split3(ld[q][0], ld[q][1], o);
-      }
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl)
-        *reinterpret_cast<u32x4*>(base + pl * PLANE + soff[q]) = o[pl];
-    }
-  };
-
-  f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  int aoff[TI], akey[TI], boff[TJ], bkey[TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i) {
-    const int row = wm * WM + i * 32 + (lane & 31);
-    aoff[i] = row * 64;
-    akey[i] = (row >> 2) & 3;
-  }
-#pragma unroll
-  for (int j = 0; j < TJ; ++j) {
-    const int row = BM + wn * WN + j * 32 + (lane & 31);
-    boff[j] = row * 64;
-    bkey[j] = (row >> 2) & 3;
-  }
-  const int hk = lane >> 5;
-  bf16x8 fa[2][3][TI], fb[2][3][TJ];        // both k steps of one tile
-  auto read = [&](auto B) {
-    const char* S = smem + decltype(B)::value * BUF;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      const int c = 2 * s + hk;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) {
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-          fa[s][pl][i] = *reinterpret_cast<const bf16x8*>(S + pl * PLANE + aoff[i] + ((c ^ akey[i]) << 4));
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-          fb[s][pl][j] = *reinterpret_cast<const bf16x8*>(S + pl * PLANE + boff[j] + ((c ^ bkey[j]) << 4));
-      }
-    }
-  };
-  auto mfma_tile = [&]() {
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j) {
-          f32x16 t = acc[i][j];
-          t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][0][i], fb[s][2][j], t, 0, 0, 0);
-          t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][2][i], fb[s][0][j], t, 0, 0, 0);
-          t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][1][i], fb[s][1][j], t, 0, 0, 0);
-          t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][0][i], fb[s][1][j], t, 0, 0, 0);
-          t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][1][i], fb[s][0][j], t, 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][0][i], fb[s][0][j], t, 0, 0, 0);
-        }
-  };
-  // memory phase of a wave: its fragments of the tile in buffer RB, its share of tile wr
-  // (registers loaded one tile earlier) into buffer 1 - RB, then its loads for tile wr + 1
-  using B0 = std::integral_constant<int, 0>;
-  using B1 = std::integral_constant<int, 1>;
-  auto mem_phase = [&](auto RB, int wr) {
-    using WB = std::integral_constant<int, 1 - decltype(RB)::value>;
-    read(RB);
-    split_store(WB{}, kbeg + wr * BK);
-    gload(kbeg + (wr + 1) * BK);
-  };
-  // one tile t held in buffer E = t & 1: G0's MFMAs while G1 reads it and writes tile t + 1,
-  // then G1's MFMAs while G0 reads tile t + 1 and writes tile t + 2.  Each group runs its own
-  // copy of the loop (the same two barriers per tile), so the accumulators never merge across a
-  // role branch and stay in place.
-  auto tile_g0 = [&](auto E, int t) {
-    using NE = std::integral_constant<int, 1 - decltype(E)::value>;
-    mfma_tile();
-    __syncthreads();
-    mem_phase(NE{}, t + 2);
-    __syncthreads();
-  };
-  auto tile_g1 = [&](auto E, int t) {
-    mem_phase(E, t + 1);
-    __syncthreads();
-    mfma_tile();
-    __syncthreads();
-  };
-
-  // prologue: tile 0 complete (all shares); G0's share of tile 1 written and its loads for tile 2
-  // issued; G1's loads for tile 1 in registers; G0 holds tile 0's fragments
-  gload(kbeg);
-  split_store(B0{}, kbeg);
-  gload(kbeg + BK);
-  if (!g1) {
-    split_store(B1{}, kbeg + BK);
-    gload(kbeg + 2 * BK);
-    __syncthreads();
-    read(B0{});
-    for (int t = 0; t < nk; t += 2) {
-      tile_g0(B0{}, t);
-      if (t + 1 < nk) tile_g0(B1{}, t + 1);
-    }
-  } else {
-    __syncthreads();
-    for (int t = 0; t < nk; t += 2) {
-      tile_g1(B0{}, t);
-      if (t + 1 < nk) tile_g1(B1{}, t + 1);
-    }
-  }
-  tile_epilogue<32, TI, TJ>(p, acc, m0 + wm * WM, n0 + wn * WN, sp,
-                            reinterpret_cast<float*>(smem) + wave * (WM * 36));
-}
-
-// gemm_x3 with specialised waves ("x3ws"): WGM x WGN consumer waves (the product tile: 4 x 2
-// waves of 64 x 64) only read the bf16 planes from LDS and issue MFMAs; 4 producer waves (one per
-// SIMD) only load the fp32 tiles, split them and write the planes.  The split's VALU and the
-// global-load waits then run in the producer wave beside the consumers' MFMA stream instead of
-// between its MFMA groups (gemm_x3 at 2 waves per SIMD: MFMA busy 0.40, half of the wave-cycles
-// waiting; MI355X PMC, profiles/r02m_*).  12 waves = 3 per SIMD: 168 VGPRs each, which both
-// roles fit (a 4 + 4 wave form with 128 x 64 consumer tiles spills at 256).  Same LDS image,
-// split and product order as gemm_x3; one block barrier per 32-k tile: consumers read buffer
-// kt & 1 while producers fill buffer (kt + 1) & 1 from registers loaded one tile earlier.
-template <int BM, int BN, int WGM, int WGN, bool MASK>
-__global__ __launch_bounds__(64 * (WGM * WGN + 4)) void gemm_x3ws(GemmArgs p) {
-  constexpr int BK = 32, NC = WGM * WGN;       // consumer waves; 4 producer waves after them
-  constexpr int WM = BM / WGM, WN = BN / WGN, TI = WM / 32, TJ = WN / 32;
-  constexpr int NPT = 256;                        // producer threads
-  constexpr int NSEG = (BM + BN) * 4 / NPT;       // 8-k segments per producer thread and tile
-  static_assert((BM + BN) * 4 % NPT == 0 && TI >= 1 && TJ >= 1, "bad x3ws tile");
-  constexpr int PLANE = (BM + BN) * 64, BUF = 3 * PLANE;
-  constexpr int STAGE = NC * WM * 36 * 4;
-  constexpr int SMEM = 2 * BUF > STAGE ? 2 * BUF : STAGE;
-  __shared__ __attribute__((aligned(1024))) char smem[SMEM];
-
-  const int mt_n = (p.M + BM - 1) / BM, nt_n = (p.N + BN - 1) / BN;
-  const int nwg = mt_n * nt_n * p.splits;
-  const int bid = xcd_swizzle(blockIdx.x, nwg);
-  const int mt = bid % mt_n, nt = (bid / mt_n) % nt_n, sp = bid / (mt_n * nt_n);
-  const int m0 = mt * BM, n0 = nt * BN;
-  const int kbeg = sp * p.kc, kend = min(p.K, kbeg + p.kc);
-  const int nk = (kend - kbeg + BK - 1) / BK;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const bool producer = __builtin_amdgcn_readfirstlane(wave) >= NC;
-
-  if (producer) {
-    const int pt = threadIdx.x - 64 * NC;
-    const float* src[NSEG];
-    int soff[NSEG], sk[NSEG];
-#pragma unroll
-    for (int q = 0; q < NSEG; ++q) {
-      const int idx = pt + q * NPT;
-      const int row = idx >> 2, c = idx & 3;
-      if (row < BM) {
-        const int gr = m0 + row < p.M ? m0 + row : 0;   // clamped rows feed unstored outputs
-        src[q] = p.A + (size_t)gr * p.lda;
-      } else {
-        const int gr = n0 + row - BM < p.N ? n0 + row - BM : 0;
-        src[q] = p.B + (size_t)gr * p.ldb;
-      }
-      soff[q] = row * 64 + ((c ^ ((row >> 2) & 3)) << 4);
-      sk[q] = c * 8;
-    }
-    using Regs = f32x4[NSEG][2];
-    auto gload = [&](Regs& ld, int k0) {
-#pragma unroll
-      for (int q = 0; q < NSEG; ++q) {
-        const int k = k0 + sk[q];
-        ld[q][0] = *reinterpret_cast<const f32x4*>(src[q] + (k < p.K ? k : 0));
-        ld[q][1] = *reinterpret_cast<const f32x4*>(src[q] + (k + 4 < p.K ? k + 4 : 0));
-      }
-    };
-    auto split_store = [&](const Regs& ld, int buf, int k0) {
-      char* base = smem + buf * BUF;
-#pragma unroll
-      for (int q = 0; q < NSEG; ++q) {
-        u32x4 o[3];
-        if constexpr (MASK) {
-          const int k = k0 + sk[q];
-          const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-          split3(k < kend ? ld[q][0] : z, k + 4 < kend ? ld[q][1] : z, o);
-        } else {
-          split3(ld[q][0], ld[q][1], o);
-        }
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          *reinterpret_cast<u32x4*>(base + pl * PLANE + soff[q]) = o[pl];
-      }
-    };
-    Regs r0, r1;
-    gload(r0, kbeg);
-    gload(r1, kbeg + BK);
-    split_store(r0, 0, kbeg);
-    __syncthreads();
-    // tile kt: tile kt + 2's loads issued, tile kt + 1 (loaded one tile ago) split into the
-    // other buffer, then the barrier that hands it to the consumers
-    for (int kt = 0; kt < nk; kt += 2) {
-      gload(r0, kbeg + (kt + 2) * BK);
-      split_store(r1, (kt + 1) & 1, kbeg + (kt + 1) * BK);
-      __syncthreads();
-      if (kt + 1 < nk) {
-        gload(r1, kbeg + (kt + 3) * BK);
-        split_store(r0, kt & 1, kbeg + (kt + 2) * BK);
-        __syncthreads();
-      }
-    }
-    return;
-  }
-
-  const int wm = wave / WGN, wn = wave % WGN;
-  f32x16 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < TJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  int aoff[TI], akey[TI], boff[TJ], bkey[TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i) {
-    const int row = wm * WM + i * 32 + (lane & 31);
-    aoff[i] = row * 64;
-    akey[i] = (row >> 2) & 3;
-  }
-#pragma unroll
-  for (int j = 0; j < TJ; ++j) {
-    const int row = BM + wn * WN + j * 32 + (lane & 31);
-    boff[j] = row * 64;
-    bkey[j] = (row >> 2) & 3;
-  }
-  const int hk = lane >> 5;
-  // fragments per unit u = (k step s, row block i): A's three planes of row block i, and W's
-  // three planes of all TJ column blocks (held for the whole step); the next unit's fragments
-  // are read while this unit's MFMAs run (double buffers indexed by the unrolled unit parity:
-  // 72 VGPRs of fragments beside the 128 of accumulators, within the 256 of two waves per SIMD)
-  bf16x8 fa[2][3], fb[2][3][TJ];
-  auto rd_a = [&](bf16x8 (&d)[3], const char* S, int s, int i) {
-    const int c = 2 * s + hk;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-      d[pl] = *reinterpret_cast<const bf16x8*>(S + pl * PLANE + aoff[i] + ((c ^ akey[i]) << 4));
-  };
-  auto rd_b = [&](bf16x8 (&d)[3][TJ], const char* S, int s, int j) {
-    const int c = 2 * s + hk;
-#pragma unroll
-    for (int pl = 0; pl < 3; ++pl)
-      d[pl][j] = *reinterpret_cast<const bf16x8*>(S + pl * PLANE + boff[j] + ((c ^ bkey[j]) << 4));
-  };
-  auto mfma6 = [&](const bf16x8 (&A)[3], const bf16x8 (&B)[3][TJ], int i, int j) {
-    f32x16 t = acc[i][j];
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[2][j], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[2], B[0][j], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[1][j], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[1][j], t, 0, 0, 0);
-    t = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[0][j], t, 0, 0, 0);
-    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[0][j], t, 0, 0, 0);
-  };
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const char* S = smem + (kt & 1) * BUF;
-#pragma unroll
-    for (int j = 0; j < TJ; ++j) rd_b(fb[0], S, 0, j);
-    rd_a(fa[0], S, 0, 0);
-#pragma unroll
-    for (int u = 0; u < 2 * TI; ++u) {
-      const int s = u / TI, i = u % TI;
-      const int s1 = (u + 1) / TI, i1 = (u + 1) % TI;
-#pragma unroll
-      for (int j = 0; j < TJ; ++j) {
-        mfma6(fa[u & 1], fb[s], i, j);
-        // after column block j's MFMAs: the next unit's A fragments (once), and at the step
-        // change step 1's W fragments of column block j, whose step-0 copy just died
-        if (u + 1 < 2 * TI) {
-          __builtin_amdgcn_sched_barrier(0);
-          if (j == 0) rd_a(fa[(u + 1) & 1], S, s1, i1);
-          if (s1 != s) rd_b(fb[s1], S, s1, j);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
-    __syncthreads();
-  }
-  tile_epilogue<32, TI, TJ, true>(p, acc, m0 + wm * WM, n0 + wn * WN, sp,
-                                  reinterpret_cast<float*>(smem) + wave * (WM * 36));
-}
-
-#ifdef AZ_TUNING   // gemm_x3 APL experiment only
-// A [M][K] (row stride lda) -> three bf16 planes [3][M][K] (plane stride `plane` elements), the
-// same split3 as gemm_x3's in-tile split, so a GEMM on the planes gives the same bits; one 8-k
-// segment per thread (K % 8 == 0)
-__global__ __launch_bounds__(256) void x3_split_kernel(const float* __restrict__ A, int lda, int M,
-                                                       int K, unsigned short* __restrict__ out,
-                                                       size_t plane) {
-  const long idx = blockIdx.x * 256L + threadIdx.x;
-  const int segs = K >> 3;
-  if (idx >= (long)M * segs) return;
-  const int r = (int)(idx / segs), c = (int)(idx % segs);
-  const float* s = A + (size_t)r * lda + c * 8;
-  u32x4 o[3];
-  split3(*reinterpret_cast<const f32x4*>(s), *reinterpret_cast<const f32x4*>(s + 4), o);
-  unsigned short* d = out + (size_t)r * K + c * 8;
-#pragma unroll
-  for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<u32x4*>(d + pl * plane) = o[pl];
-}
-
-#endif
 
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs p) {
   const long total = (long)p.M * p.N;
@@ -3093,148 +2233,6 @@ __global__ __launch_bounds__(256, 2) void c4_leaf_kernel(LeafArgs a) {   // <= 2
 static unsigned long long* g_leaf_trace = nullptr;
 #endif
 
-// --------------------------------------------------------------------- K-sliced row panels
-// C = epi(A . W^T) for mid-size M (the B = 512 output_transform: 512 x 3136 x 3136).  A tile
-// grid cannot fill 256 CUs there without split-K, whose slabs cost a 32 MB write + re-read and
-// a reduce launch per call.  Here block (mb, nb) owns 32 rows x one column panel over the WHOLE
-// K (16 x 16 blocks for that shape: one per CU, no slabs):
-//   - column panels are 16*CT wide except the first n_narrow, which are 16 narrower (3136 =
-//     12 x 192 + 4 x 208); every block computes CT sub-tiles, so a narrow panel's last one
-//     overlaps its neighbour (computed, not stored) and no row of W is ever out of range -- the
-//     lanes need no clamps, hence one base pointer each instead of 15;
-//   - its KW waves split K into KW contiguous slices; each wave streams its A and W fragments
-//     straight from L2 into registers (double-buffered: the next step's loads fly under this
-//     step's MFMAs), so the loop has no LDS traffic and no barriers;
-//   - MFMA (h, t) of a step takes k = 16h + 4g + t in lane group g for both operands (a
-//     bijection of the step's k values);
-//   - the partial tiles meet in LDS and are summed in wave order (deterministic), then bias /
-//     activation and float4 stores.
-// One wave's share of a gemm_kslice block: NC column sub-tiles starting at sub-tile cs0, the
-// 32 rows, k steps [it0, it1) of 32; the partial tile goes to LDS slot `slot` (row stride SP).
-template <int NC, int SP>
-__device__ __forceinline__ void kslice_wave(const GemmArgs& p, int m0, int n0, int cs0, int it0,
-                                            int it1, float* slot) {
-  constexpr int RT = 2;
-  const int lane = threadIdx.x & 63, g = lane >> 4, c16 = lane & 15;
-  // buffer loads: one 32-bit per-lane byte offset per operand plus a wave-uniform SGPR offset
-  // per 16-row sub-tile (no hoisted 64-bit addresses)
-  const __amdgpu_buffer_rsrc_t ra =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.A), 0, p.M * p.lda * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.B), 0, p.N * p.ldb * 4, 0x00020000);
-  const int va = ((m0 + c16) * p.lda + 4 * g) * 4;               // host: M % 32 == 0
-  const int vb = ((n0 + cs0 * 16 + c16) * p.ldb + 4 * g) * 4;    // rows < N by the panel layout
-  const int sa = 16 * p.lda * 4, sb = 16 * p.ldb * 4;
-  f32x4 acc[RT][NC];
-#pragma unroll
-  for (int rs = 0; rs < RT; ++rs)
-#pragma unroll
-    for (int cs = 0; cs < NC; ++cs) acc[rs][cs] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // step `it` covers k in [32 it, 32 it + 32); lane group g holds k = 16h + 4g .. +3 of half h
-  auto load = [&](f32x4 (&a)[RT][2], f32x4 (&b)[NC][2], int it) {
-    const int k = it * 32;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-#pragma unroll
-      for (int rs = 0; rs < RT; ++rs)
-        a[rs][h] = __builtin_bit_cast(
-            f32x4, __builtin_amdgcn_raw_buffer_load_b128(ra, va + (k + 16 * h) * 4, rs * sa, 0));
-#pragma unroll
-      for (int cs = 0; cs < NC; ++cs)
-        b[cs][h] = __builtin_bit_cast(
-            f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, vb + (k + 16 * h) * 4, cs * sb, 0));
-    }
-  };
-  // MFMA (h, t) of a step takes k = 16h + 4g + t in lane group g for both operands
-  auto mma = [&](const f32x4 (&a)[RT][2], const f32x4 (&b)[NC][2]) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int rs = 0; rs < RT; ++rs)
-#pragma unroll
-          for (int cs = 0; cs < NC; ++cs)
-            acc[rs][cs] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[rs][h][t], b[cs][h][t],
-                                                               acc[rs][cs], 0, 0, 0);
-  };
-  f32x4 a0[RT][2], b0[NC][2], a1[RT][2], b1[NC][2];
-  int it = it0;
-  if (it < it1) load(a0, b0, it);
-  // sched_barrier: the next step's loads stay issued BEFORE this step's MFMAs (left alone, the
-  // scheduler sinks them behind the MFMAs and the prefetch distance collapses)
-  for (; it + 1 < it1; it += 2) {
-    load(a1, b1, it + 1);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(a0, b0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (it + 2 < it1) load(a0, b0, it + 2);
-    __builtin_amdgcn_sched_barrier(0);
-    mma(a1, b1);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if (it < it1) mma(a0, b0);
-#pragma unroll
-  for (int rs = 0; rs < RT; ++rs)
-#pragma unroll
-    for (int cs = 0; cs < NC; ++cs)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        slot[(rs * 16 + 4 * g + r) * SP + (cs0 + cs) * 16 + c16] = acc[rs][cs][r];
-}
-
-// 512 threads: wave w takes K slice w & 3 (of 4) and column half w >> 2 (sub-tiles 0..CT0-1 or
-// CT0..CT0+CT1-1); the two waves of a SIMD (w, w + 4) hold CT0 + CT1 sub-tiles between them, so
-// every SIMD does the same MFMA work and has two waves to issue it.
-template <int CT0, int CT1>
-__global__ __launch_bounds__(512) void gemm_kslice(GemmArgs p, int n_narrow) {
-  constexpr int CT = CT0 + CT1;
-  constexpr int SP = 16 * CT + 4;           // partial-tile row stride: conflict-free writes
-  __shared__ __attribute__((aligned(16))) float part[4 * 32 * SP];
-  const int wave = threadIdx.x >> 6;
-  // XCD-aware placement (1-D grid, block id b runs on XCD b % 8): each XCD owns nb / 8 whole
-  // column panels and all row blocks of them, so a W panel is fetched into ONE L2 and shared by
-  // the row blocks there (host: nb % 8 == 0)
-  const int mb = p.M / 32, nb = gridDim.x / mb;
-  const int per = nb / 8, j = blockIdx.x >> 3;
-  const int by = (blockIdx.x & 7) * per + j % per, bx = j / per;
-  const int m0 = bx * 32;
-  const int n0 = by < n_narrow ? by * (16 * CT - 16)
-                               : n_narrow * (16 * CT - 16) + (by - n_narrow) * 16 * CT;
-  const int cw = by < n_narrow ? 16 * CT - 16 : 16 * CT;      // columns this block stores
-  const int nit = p.K / 32;                 // host: K % 32 == 0
-  const int ks = wave & 3;
-  const int it0 = nit * ks / 4, it1 = nit * (ks + 1) / 4;
-  float* slot = part + ks * 32 * SP;
-  if (wave < 4) kslice_wave<CT0, SP>(p, m0, n0, 0, it0, it1, slot);
-  else kslice_wave<CT1, SP>(p, m0, n0, CT0, it0, it1, slot);
-  __syncthreads();
-  const int c4n = cw / 4;
-  for (int i = threadIdx.x; i < 32 * c4n; i += 512) {
-    const int row = i / c4n, c4 = (i % c4n) * 4;
-    const float* q = part + row * SP + c4;
-    f32x4 v = *reinterpret_cast<const f32x4*>(q);
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const f32x4 u = *reinterpret_cast<const f32x4*>(q + w * 32 * SP);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) v[c] += u[c];
-    }
-    epilogue_store4(p, m0 + row, n0 + c4, v);
-  }
-}
-
-// gemm_kslice<7, 6> covers the shape when 16 column panels of 192 / 208 columns tile N exactly
-// and 32-row blocks x 16 panels make one round of 256 blocks (M = 512, N = 3072 .. 3328: the
-// B = 512 output_transform).  Returns the number of narrow (192) panels, or -1.
-static int kslice_narrow(const GemmArgs& a) {
-  if (a.M != 512 || a.K % 32 != 0 || a.K < 1024 || a.lda % 4 != 0 || a.ldb % 4 != 0 || !a.vec_epi)
-    return -1;
-  const int nb = 16;
-  if (a.N % 16 != 0 || a.N < 192 * nb || a.N > 208 * nb) return -1;
-  return nb - (a.N - 192 * nb) / 16;        // 208 x (nb - n) + 192 x n = N
-}
-
 // ------------------------------------------------------------------------ tall-skinny GEMM
 // C[M][N] = epi(A[M][K] . W[N][K]^T) for the grid-graph layers: M ~ 10^5..10^6 rows, K in
 // {64, 128}, N in {64, 128, 256}.  A tile kernel with K <= 128 spends most of each block on its
@@ -3370,32 +2368,19 @@ static bool launch_tall(const GemmArgs& a, hipStream_t s) {
   return false;
 }
 
-struct TileCfg { int bm, bn, bk, wgm, wgn; };
-// register-staged: 0: 64x64x32 (4 waves 2x2)   1: 128x128x32 (4 waves 2x2)   2: 64x64x64
-// 3: 128x64x32 (4 waves 2x2)  4: 128x128x32 (8 waves 2x4)   5: 256x128x32 (8 waves 4x2)
-// LDS-DMA (K-major A and B only): 6: 128x128x32 (4 waves 2x2)  7: 64x64x32  8: 128x64x32
-// 9: 128x128x32 (8 waves 2x4)
-// multi-stage LDS-DMA: 10: 128x128x16 x4 buffers  11: 128x128x32 x3  12: 128x64x32 x3
-// 13: 128x128x16 x3  14: 128x64x16 x4
-// LDS-DMA v2 (fragments of the whole k-tile read up front): 15: 128x128 mfma32  16: 128x128
-// mfma16  17: 128x64 mfma16  18: 128x64 mfma32  19: 128x128 mfma16 (8 waves 2x4)
-// v2 + DMA issue interleaved with the MFMAs: 20: 128x128 mfma32  21: 128x128 mfma16
-// 22: 128x64 mfma16
-// 8-wave 1-block-per-CU tiles (6 DMA pieces per 64 MFMAs instead of 8): 23: 256x128 (glds)
-// 24: 256x128 (v2, mfma16)  25: 128x256 (v2, mfma16)  26/27: 256x128 interleaved DMA issue
-// (mfma16 / mfma32)  28: 256x128 (v2, mfma32)
-static const TileCfg kCfgs[] = {{64, 64, 32, 2, 2},  {128, 128, 32, 2, 2}, {64, 64, 64, 2, 2},
-                                {128, 64, 32, 2, 2}, {128, 128, 32, 2, 4}, {256, 128, 32, 4, 2},
-                                {128, 128, 32, 2, 2}, {64, 64, 32, 2, 2},  {128, 64, 32, 2, 2},
-                                {128, 128, 32, 2, 4}, {128, 128, 16, 2, 2}, {128, 128, 32, 2, 2},
-                                {128, 64, 32, 2, 2},  {128, 128, 16, 2, 2}, {128, 64, 16, 2, 2},
-                                {128, 128, 32, 2, 2}, {128, 128, 32, 2, 2}, {128, 64, 32, 2, 2},
-                                {128, 64, 32, 2, 2},  {128, 128, 32, 2, 4}, {128, 128, 32, 2, 2},
-                                {128, 128, 32, 2, 2}, {128, 64, 32, 2, 2},  {256, 128, 32, 4, 2},
-                                {256, 128, 32, 4, 2}, {128, 256, 32, 2, 4}, {256, 128, 32, 4, 2},
-                                {256, 128, 32, 4, 2}, {256, 128, 32, 4, 2}, {256, 128, 32, 4, 2},
-                                {256, 128, 32, 4, 2}, {256, 128, 32, 4, 2}, {256, 128, 32, 4, 2}};
-constexpr int kNumCfgs = 33;
+// The fp32 MFMA tiles.  The product dispatch (gemm_f32_partial) picks among the first four; the
+// two ring forms of the 256x128 tile are the tuning build's (AZ_GEMM_RING = 3 / 4).
+enum Tile {
+  TILE_REG_64x64,         // register-staged 64x64x32, 4 waves 2x2: any operand layout
+  TILE_GLDS_128x128,      // LDS-DMA (K-major A and B only from here on), 4 waves 2x2
+  TILE_GLDS_128x64,       // LDS-DMA, 4 waves 2x2
+  TILE_GLDS2_256x128,     // LDS-DMA v2, 8 waves 4x2, one block per CU
+  TILE_RING_256x128,      // ... with the three-buffer ring
+  TILE_RING_ST_256x128,   // ... and its stagger
+};
+struct TileCfg { int bm, bn, bk; };
+static const TileCfg kCfgs[] = {{64, 64, 32},   {128, 128, 32}, {128, 64, 32},
+                                {256, 128, 32}, {256, 128, 32}, {256, 128, 32}};
 
 template <int BM, int BN, int BK, int WGM, int WGN>
 static void launch_tile(const GemmArgs& a, bool akm, bool bkm, hipStream_t s) {
@@ -3413,56 +2398,21 @@ static void launch_glds(const GemmArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((gemm_f32_glds<BM, BN, WGM, WGN>), dim3(nwg), dim3(64 * WGM * WGN), 0, s, a);
 }
 
-template <int BM, int BN, int BK, int NBUF>
-static void launch_pipe(const GemmArgs& a, hipStream_t s) {
-  const int nwg = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * a.splits;
-  hipLaunchKernelGGL((gemm_f32_glds_pipe<BM, BN, BK, NBUF, 2, 2>), dim3(nwg), dim3(256), 0, s, a);
-}
-
-template <int BM, int BN, int WGM, int WGN, int MF, bool IL = false, int NB = 2, bool ST = false>
+template <int BM, int BN, int WGM, int WGN, int NB = 2, bool ST = false>
 static void launch_glds2(const GemmArgs& a, hipStream_t s) {
   const int nwg = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * a.splits;
-  hipLaunchKernelGGL((gemm_f32_glds2<BM, BN, WGM, WGN, MF, IL, NB, ST>), dim3(nwg),
-                     dim3(64 * WGM * WGN), 0, s, a);
+  hipLaunchKernelGGL((gemm_f32_glds2<BM, BN, WGM, WGN, NB, ST>), dim3(nwg), dim3(64 * WGM * WGN),
+                     0, s, a);
 }
 
-static void launch_cfg(int cfg, const GemmArgs& a, bool akm, bool bkm, hipStream_t s) {
-  // the product dispatch uses configs 0, 6, 8 and 24 (gemm_f32_partial); every other tile is a
-  // measured-slower experiment, compiled only into the tuning build
+static void launch_cfg(Tile cfg, const GemmArgs& a, bool akm, bool bkm, hipStream_t s) {
   switch (cfg) {
-    case 24: launch_glds2<256, 128, 4, 2, 16>(a, s); break;
-    case 6: launch_glds<128, 128, 2, 2>(a, s); break;
-    case 8: launch_glds<128, 64, 2, 2>(a, s); break;
+    case TILE_GLDS2_256x128: launch_glds2<256, 128, 4, 2>(a, s); break;
+    case TILE_GLDS_128x128: launch_glds<128, 128, 2, 2>(a, s); break;
+    case TILE_GLDS_128x64: launch_glds<128, 64, 2, 2>(a, s); break;
 #ifdef AZ_TUNING
-    case 15: launch_glds2<128, 128, 2, 2, 32>(a, s); break;
-    case 16: launch_glds2<128, 128, 2, 2, 16>(a, s); break;
-    case 17: launch_glds2<128, 64, 2, 2, 16>(a, s); break;
-    case 18: launch_glds2<128, 64, 2, 2, 32>(a, s); break;
-    case 19: launch_glds2<128, 128, 2, 4, 16>(a, s); break;
-    case 23: launch_glds<256, 128, 4, 2>(a, s); break;
-    case 25: launch_glds2<128, 256, 2, 4, 16>(a, s); break;
-    case 26: launch_glds2<256, 128, 4, 2, 16, true>(a, s); break;
-    case 27: launch_glds2<256, 128, 4, 2, 32, true>(a, s); break;
-    case 28: launch_glds2<256, 128, 4, 2, 32>(a, s); break;
-    case 29: launch_glds2<256, 128, 4, 2, 16, false, 3>(a, s); break;
-    case 30: launch_glds2<256, 128, 4, 2, 32, false, 3>(a, s); break;
-    case 31: launch_glds2<256, 128, 4, 2, 16, false, 3, true>(a, s); break;
-    case 32: launch_glds2<256, 128, 4, 2, 32, false, 3, true>(a, s); break;
-    case 20: launch_glds2<128, 128, 2, 2, 32, true>(a, s); break;
-    case 21: launch_glds2<128, 128, 2, 2, 16, true>(a, s); break;
-    case 22: launch_glds2<128, 64, 2, 2, 16, true>(a, s); break;
-    case 10: launch_pipe<128, 128, 16, 4>(a, s); break;
-    case 11: launch_pipe<128, 128, 32, 3>(a, s); break;
-    case 12: launch_pipe<128, 64, 32, 3>(a, s); break;
-    case 13: launch_pipe<128, 128, 16, 3>(a, s); break;
-    case 14: launch_pipe<128, 64, 16, 4>(a, s); break;
-    case 7: launch_glds<64, 64, 2, 2>(a, s); break;
-    case 9: launch_glds<128, 128, 2, 4>(a, s); break;
-    case 1: launch_tile<128, 128, 32, 2, 2>(a, akm, bkm, s); break;
-    case 2: launch_tile<64, 64, 64, 2, 2>(a, akm, bkm, s); break;
-    case 3: launch_tile<128, 64, 32, 2, 2>(a, akm, bkm, s); break;
-    case 4: launch_tile<128, 128, 32, 2, 4>(a, akm, bkm, s); break;
-    case 5: launch_tile<256, 128, 32, 4, 2>(a, akm, bkm, s); break;
+    case TILE_RING_256x128: launch_glds2<256, 128, 4, 2, 3>(a, s); break;
+    case TILE_RING_ST_256x128: launch_glds2<256, 128, 4, 2, 3, true>(a, s); break;
 #endif
     default: launch_tile<64, 64, 32, 2, 2>(a, akm, bkm, s); break;
   }
@@ -3480,16 +2430,9 @@ static bool try_gemv_full(const GemmArgs& a, hipStream_t s) {
 }
 
 // whole-K kernel when A's rows fit 32 KB of LDS (S = ceil(K/256) rounded up to an
-// instantiated width); AZ_GEMV_R=1 selects one weight row per wave instead of two
+// instantiated width), two weight rows per wave
 template <int MR>
 static bool launch_gemv_full(const GemmArgs& a, hipStream_t s) {
-#ifdef AZ_TUNING
-  static const bool r1 = [] { const char* e = tuning_env("AZ_GEMV_R"); return e && atoi(e) == 1; }();
-  if (r1)
-    return try_gemv_full<MR, 1, 1>(a, s) || try_gemv_full<MR, 2, 1>(a, s) ||
-           try_gemv_full<MR, 4, 1>(a, s) || try_gemv_full<MR, 8, 1>(a, s) ||
-           try_gemv_full<MR, 13, 1>(a, s) || try_gemv_full<MR, 16, 1>(a, s);
-#endif
   return try_gemv_full<MR, 1, 2>(a, s) || try_gemv_full<MR, 2, 2>(a, s) ||
          try_gemv_full<MR, 4, 2>(a, s) || try_gemv_full<MR, 8, 2>(a, s) ||
          try_gemv_full<MR, 13, 2>(a, s) || try_gemv_full<MR, 16, 2>(a, s);
@@ -3498,20 +2441,7 @@ static bool launch_gemv_full(const GemmArgs& a, hipStream_t s) {
 static void launch_gemv(const GemmArgs& a, hipStream_t s) {
   static const bool chunked = tuning_env("AZ_GEMV_CHUNKED") != nullptr;   // A/B experiments
   if (!chunked && a.M >= 3 && a.K > 256 * 8 && a.K <= 256 * 13) {
-#ifdef AZ_TUNING   // AZ_GEMV_ROWS=<MG><R>: rows per LDS group, weight rows per wave (A/B runs)
-    static const char* env_rows = tuning_env("AZ_GEMV_ROWS");
-    const int v = env_rows ? atoi(env_rows) : 22;
-    switch (v) {
-      case 42: hipLaunchKernelGGL((gemv_rows<13, 2, 4>), dim3((a.N + 7) / 8), dim3(256), 0, s, a); return;
-      case 82: hipLaunchKernelGGL((gemv_rows<13, 2, 8>), dim3((a.N + 7) / 8), dim3(256), 0, s, a); return;
-      case 41: hipLaunchKernelGGL((gemv_rows<13, 1, 4>), dim3((a.N + 3) / 4), dim3(256), 0, s, a); return;
-      case 44: hipLaunchKernelGGL((gemv_rows<13, 4, 4>), dim3((a.N + 15) / 16), dim3(256), 0, s, a); return;
-      case 12: hipLaunchKernelGGL((gemv_rows<13, 2, 1>), dim3((a.N + 7) / 8), dim3(256), 0, s, a); return;
-      default: break;
-    }
-#endif
-    // 2 rows per LDS group: 10.6 us at M = 3..4, 14.6 at M = 8 vs 16.4 / 25.2 with 4-row groups
-    // and 9.9 / 15.7 with 1 (tools/gemv_probe.py on MI355X)
+    // 2 rows per LDS group, 2 weight rows per wave
     hipLaunchKernelGGL((gemv_rows<13, 2, 2>), dim3((a.N + 7) / 8), dim3(256), 0, s, a);
     return;
   }
@@ -3543,7 +2473,7 @@ static void plan(GemmArgs& a, int bm, int bn, int bk, size_t ws_bytes) {
   if (env_split && a.slab) {
     S = std::max(1, atoi(env_split));
   } else if (tiles < 1024 && a.slab) {
-    // measured on MI355X (tools/gemm_sweep.py): M=512 x 3136^2 best at S=3 (1176 blocks),
+    // measured on MI355X: M=512 x 3136^2 best at S=3 (1176 blocks),
     // M=64 at S=4..8; keep >= 4 BK steps per split
     S = (int)std::min<long>(std::min<long>((1024 + tiles - 1) / tiles, 8), a.K / (bk * 4));
   }
@@ -3558,7 +2488,7 @@ static void plan(GemmArgs& a, int bm, int bn, int bk, size_t ws_bytes) {
 // a CU (64 KB of LDS each), so the launch runs in ceil(blocks / 256) block-rounds per CU, each
 // as long as one split's k-tiles; two co-resident blocks hide each other's latency (~1.1x,
 // measured), and every extra split costs an M x N slab written and re-read.  The model
-// reproduces the MI355X sweep ranking (tools/gemm_sweep.py glds: M=512 -> S=5, M=256 -> S=5).
+// reproduces the MI355X sweep ranking (M=512 -> S=5, M=256 -> S=5).
 static int glds_splits(const GemmArgs& a, long tiles, size_t ws_bytes) {
   const int bk = 32;
   int best = 1;
@@ -3779,194 +2709,77 @@ __global__ __launch_bounds__(512) void splitk_reduce_split_kernel(GemmArgs p,
 }
 
 
-// W row-scale cache: weights change only between calls that say so (az_weights_changed, which
-// az_adam_f32 also calls; the Python parameter store calls it on every load / copy), so a
-// weight matrix's scales are computed once per weight update.  Each entry has two buffers: a
-// recompute writes the other one and synchronises its stream before publishing it, so a GEMM
-// launched earlier on another stream keeps reading consistent scales, and one launched later on
-// any stream sees finished ones.
-static std::atomic<long> g_wgen{1};
-struct WScaleEntry {
-  const float* w;
-  int n, k, ld;
-  long gen;                    // generation buf[cur] (the in-tile GEMM's row scales) is from
-  float* buf[2];
-  int cur;
-  unsigned short* planes[2];   // the P2 GEMM's W planes [2][n][k] (nullptr until first asked)
-  float* pbuf[2];              // their row scales: a double buffer of its own, so a recompute
-  int pcur;                    // of one kind never overwrites the other kind's live buffer
-  long pgen;                   // generation planes[pcur] / pbuf[pcur] were split at
-  float* frags[2];             // conv2's fp16 fragment planes for the trunk (conv2_planes)
-  int fcur;
-  long fgen;
-};
-
-static std::mutex g_wmu;
-static std::vector<WScaleEntry> g_wcache;
-
-// Composed heads cache (composed_heads below): one entry per (W2, b2, fc_policy.weight / .bias,
-// fc_value.weight / .bias, F, A) whose six tensors all lie in registered parameter storage, kept
-// per weight generation like the planes above (double buffer, the recompute synchronises its
-// stream before publishing; az_weights_unregister frees it).
-struct ComposedEntry {
-  const float* in[6];
-  int F, A;
-  float* buf[2];               // Wc [A + 1][F], then bc [A + 1]
-  double* part;                // the compose kernels' fp64 partials (same allocation as buf)
-  int cur;
-  long gen;
-};
-static std::vector<ComposedEntry> g_ccache;   // under g_wmu
-
-// the entry of (w, n, k, ld), created on first use (caller holds g_wmu); nullptr when out of memory
-static WScaleEntry* wcache_entry(const float* w, int n, int k, int ld) {
-  for (auto& x : g_wcache)
-    if (x.w == w && x.n == n && x.k == k && x.ld == ld) return &x;
-  WScaleEntry x{w, n, k, ld, 0, {nullptr, nullptr}, 1, {nullptr, nullptr}, {nullptr, nullptr},
-                1, 0, {nullptr, nullptr}, 1, 0};
-  if (hipMalloc(&x.buf[0], (size_t)8 * n * sizeof(float)) != hipSuccess) return nullptr;
-  x.buf[1] = x.buf[0] + 2 * n;
-  x.pbuf[0] = x.buf[0] + 4 * n;
-  x.pbuf[1] = x.buf[0] + 6 * n;
-  g_wcache.push_back(x);
-  return &g_wcache.back();
-}
-
-// Parameter storage the caller registered (az_weights_register): only weights inside it are
-// cached -- anywhere else a pointer says nothing about the values behind it (a freed tensor's
-// memory can hold the next one), so their scales are computed per call and the pre-split planes
-// are not used.
-static std::mutex g_regmu;
-static std::vector<std::pair<uintptr_t, uintptr_t>> g_regs;
-
-static bool weights_registered(const float* w, int n, int k, int ld) {
-  const uintptr_t b = reinterpret_cast<uintptr_t>(w);
-  const uintptr_t e = b + ((size_t)(n - 1) * ld + k) * sizeof(float);
-  std::lock_guard<std::mutex> lk(g_regmu);
-  for (const auto& r : g_regs)
-    if (b >= r.first && e <= r.second) return true;
-  return false;
-}
-
-}  // namespace az
-extern "C" int az_weights_changed(void) {
-  az::g_wgen.fetch_add(1);
-  return AZ_OK;
-}
-extern "C" int az_weights_register(const void* base, size_t bytes) {
-  AZ_REQUIRE(base && bytes > 0, AZ_EINVAL, "az_weights_register: null / empty range");
-  {
-    std::lock_guard<std::mutex> lk(az::g_regmu);
-    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
-    az::g_regs.emplace_back(b, b + bytes);
+// splitk_reduce, and C's rows split for a P2 GEMM that takes C as its A (PreSplitA{planes, sc}:
+// planes [2][M][N] fp16, sc [2][M]); C's bits are splitk_reduce's.  Returns 1 when launched, 0 when
+// the shapes / epilogue do not qualify (nothing launched: the caller reduces the usual way), or a
+// negative AZ_E* code.
+int splitk_reduce_split(const az_gemm_desc* d, int splits, unsigned short* planes, float* sc,
+                        hipStream_t s, bool write_c) {
+  if (!(splits >= 2 && splits <= 8 && d->N % 32 == 0 && d->N <= 4096 && d->M > 0 && !d->C2 &&
+        !d->R && !d->G && !d->c_rows && d->beta == 0.f &&
+        (d->act == AZ_ACT_NONE || d->act == AZ_ACT_RELU) && d->ldc % 4 == 0 && aligned16(d->C) &&
+        (!d->bias || aligned16(d->bias)) && aligned16(d->ws) && planes && sc &&
+        aligned16(planes)))
+    return 0;
+  GemmArgs a = {};
+  a.M = d->M; a.N = d->N;
+  a.bias = d->bias; a.act = d->act; a.C = write_c ? d->C : nullptr; a.ldc = d->ldc;
+  a.slab = static_cast<float*>(d->ws);
+  a.splits = splits;
+  // one 8-column chunk per thread (N = 3,136: 7 waves; 8.5 -> 8.35 us per M = 512 launch against
+  // two chunks on 4 waves, profiles/r06/reduce_ab)
+  const int T = (d->N / 8 + 63) / 64 * 64;
+  switch (splits) {
+#define AZ_RS(SS) case SS: hipLaunchKernelGGL((splitk_reduce_split_kernel<SS, 1>), dim3(a.M), dim3(T), \
+                                             0, s, a, planes, sc); break;
+    AZ_RS(2) AZ_RS(3) AZ_RS(4) AZ_RS(5) AZ_RS(6) AZ_RS(7) default: AZ_RS(8)
+#undef AZ_RS
   }
-  return az_weights_changed();           // a reused range must not meet old cache entries
-}
-extern "C" int az_weights_unregister(const void* base) {
-  std::vector<std::pair<uintptr_t, uintptr_t>> gone;
-  {
-    std::lock_guard<std::mutex> lk(az::g_regmu);
-    const uintptr_t b = reinterpret_cast<uintptr_t>(base);
-    for (size_t i = 0; i < az::g_regs.size();)
-      if (az::g_regs[i].first == b) {
-        gone.push_back(az::g_regs[i]);
-        az::g_regs.erase(az::g_regs.begin() + i);
-      } else {
-        ++i;
-      }
-  }
-  // free the cache entries (row scales + fp16 planes: 8 N K bytes per weight, 79 MB for a
-  // 3136 x 3136 one) of weights inside the range, once no launched GEMM can still read them
-  if (!gone.empty()) {
-    std::lock_guard<std::mutex> lk(az::g_wmu);
-    bool synced = false;
-    for (size_t i = 0; i < az::g_ccache.size();) {   // composed heads with any input in the range
-      bool inside = false;
-      for (const float* p : az::g_ccache[i].in) {
-        const uintptr_t w = reinterpret_cast<uintptr_t>(p);
-        for (const auto& r : gone) inside |= w >= r.first && w < r.second;
-      }
-      if (!inside) {
-        ++i;
-        continue;
-      }
-      if (!synced) {
-        AZ_REQUIRE(hipDeviceSynchronize() == hipSuccess, AZ_EDEVICE,
-                   "az_weights_unregister: hipDeviceSynchronize failed");
-        synced = true;
-      }
-      (void)hipFree(az::g_ccache[i].buf[0]);
-      az::g_ccache.erase(az::g_ccache.begin() + i);
-    }
-    for (size_t i = 0; i < az::g_wcache.size();) {
-      const uintptr_t w = reinterpret_cast<uintptr_t>(az::g_wcache[i].w);
-      bool inside = false;
-      for (const auto& r : gone) inside |= w >= r.first && w < r.second;
-      if (!inside) {
-        ++i;
-        continue;
-      }
-      if (!synced) {
-        AZ_REQUIRE(hipDeviceSynchronize() == hipSuccess, AZ_EDEVICE,
-                   "az_weights_unregister: hipDeviceSynchronize failed");
-        synced = true;
-      }
-      (void)hipFree(az::g_wcache[i].buf[0]);
-      if (az::g_wcache[i].planes[0]) (void)hipFree(az::g_wcache[i].planes[0]);
-      if (az::g_wcache[i].frags[0]) (void)hipFree(az::g_wcache[i].frags[0]);
-      az::g_wcache.erase(az::g_wcache.begin() + i);
-    }
-  }
-  return az_weights_changed();
-}
-namespace az {
-
-static const float* w_row_scales(const float* w, int n, int k, int ld, hipStream_t s) {
-  if (!weights_registered(w, n, k, ld)) return nullptr;   // the caller computes them per call
-  const long gen = g_wgen.load();
-  std::lock_guard<std::mutex> lk(g_wmu);
-  WScaleEntry* e = wcache_entry(w, n, k, ld);
-  if (!e) return nullptr;
-  if (e->gen == gen) return e->buf[e->cur];
-  const int nxt = e->cur ^ 1;
-  hipLaunchKernelGGL(row_scale_kernel, dim3(n), dim3(256), 0, s, w, n, k, ld, H3_TW,
-                     e->buf[nxt]);
-  if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
-  e->cur = nxt;
-  e->gen = gen;
-  return e->buf[nxt];
+  const int rc = check_launch("splitk_reduce_split_kernel");
+  return rc == AZ_OK ? 1 : rc;
 }
 
-// W's fp16 planes and scales for the P2 GEMM, cached like the scales above (two buffers, the
-// recompute synchronises its stream before publishing); nullptr when memory is short.
-static const unsigned short* w_planes(const float* w, int n, int k, int ld, hipStream_t s,
-                                      const float** scales) {
-  if (!weights_registered(w, n, k, ld)) return nullptr;
-  const long gen = g_wgen.load();
-  std::lock_guard<std::mutex> lk(g_wmu);
-  WScaleEntry* e = wcache_entry(w, n, k, ld);
-  if (!e) return nullptr;
-  if (!e->planes[0]) {
-    const size_t one = (size_t)2 * n * k;
-    if (hipMalloc(&e->planes[0], 2 * one * sizeof(unsigned short)) != hipSuccess) {
-      e->planes[0] = nullptr;
-      return nullptr;
-    }
-    e->planes[1] = e->planes[0] + one;
-    e->pgen = 0;
+// The two kernels for the weights cache (az_weights.hip w_row_scales / w_planes); launch_x3 runs
+// them on A's rows (and on the W of unregistered weights) per call
+void launch_row_scale(const float* X, int rows, int cols, int ld, int T, float* out,
+                      hipStream_t s) {
+  hipLaunchKernelGGL(row_scale_kernel, dim3(rows), dim3(256), 0, s, X, rows, cols, ld, T, out);
+}
+void launch_h3_split_rows(const float* X, int rows, int cols, int ld, int T, unsigned short* out,
+                          float* sc, hipStream_t s) {
+  hipLaunchKernelGGL(h3_split_rows_kernel, dim3(rows), dim3(256), 0, s, X, rows, cols, ld, T, out,
+                     sc);
+}
+
+// The Connect4 trunk's conv2 weights ([64][32][3][3]) as the fp16 planes of its MFMA B fragments
+// (az_trunk.hip c4_trunk_tile), made once per weight generation instead of by every wave of every
+// block: wave nt (block nt) gathers each lane's 72 weights -- step s = tap * 8 + j takes
+// w2[co][ci][tap], co = 16 nt + (lane & 15), ci = 8 (lane >> 4) + j -- and runs w2_planes itself,
+// so the planes are bit for bit what the trunk would compute.  Layout: 16-B unit
+// [(nt * 18 + t) * 64 + lane] = tap t's high plane, [(nt * 18 + 9 + t) * 64 + lane] its low plane
+// (18 coalesced 1-KB loads per wave), then float [W2P_UNITS * 4 + nt * 64 + lane] = the lane's
+// channel's 1 / scale.
+__global__ __launch_bounds__(64) void c4_w2_planes_kernel(const float* __restrict__ w2,
+                                                          float* __restrict__ out) {
+  const int nt = blockIdx.x, lane = threadIdx.x;
+  const int co = 16 * nt + (lane & 15), h = lane >> 4;
+  float breg[72];
+#pragma unroll
+  for (int st = 0; st < 72; ++st) breg[st] = w2[co * 288 + (8 * h + (st & 7)) * 9 + (st >> 3)];
+  bf16x8 bh[9], bl[9];
+  const float iw = w2_planes(breg, bh, bl);
+  u32x4* const u = reinterpret_cast<u32x4*>(out);
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    u[(nt * 18 + t) * 64 + lane] = __builtin_bit_cast(u32x4, bh[t]);
+    u[(nt * 18 + 9 + t) * 64 + lane] = __builtin_bit_cast(u32x4, bl[t]);
   }
-  if (e->pgen == gen) {
-    *scales = e->pbuf[e->pcur];
-    return e->planes[e->pcur];
-  }
-  const int nxt = e->pcur ^ 1;
-  hipLaunchKernelGGL(h3_split_rows_kernel, dim3(n), dim3(256), 0, s, w, n, k, ld, H3_TW,
-                     e->planes[nxt], e->pbuf[nxt]);
-  if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
-  e->pcur = nxt;
-  e->pgen = gen;
-  *scales = e->pbuf[nxt];
-  return e->planes[nxt];
+  out[W2P_UNITS * 4 + nt * 64 + lane] = iw;
+}
+
+// c4_w2_planes_kernel on stream s, for the weights cache (conv2_planes)
+void launch_c4_w2_planes(const float* w2, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(c4_w2_planes_kernel, dim3(4), dim3(64), 0, s, w2, out);
 }
 
 template <int CTRL>
@@ -4077,250 +2890,6 @@ __global__ __launch_bounds__(256) void heads_tiles_finalize_kernel(HeadsEpi he, 
   he.v[row] = tanhf(s[8] + he.bv[0]);
 }
 
-// The Connect4 trunk's conv2 weights ([64][32][3][3]) as the fp16 planes of its MFMA B fragments
-// (az_trunk.hip c4_trunk_tile), made once per weight generation instead of by every wave of every
-// block: wave nt (block nt) gathers each lane's 72 weights -- step s = tap * 8 + j takes
-// w2[co][ci][tap], co = 16 nt + (lane & 15), ci = 8 (lane >> 4) + j -- and runs w2_planes itself,
-// so the planes are bit for bit what the trunk would compute.  Layout: 16-B unit
-// [(nt * 18 + t) * 64 + lane] = tap t's high plane, [(nt * 18 + 9 + t) * 64 + lane] its low plane
-// (18 coalesced 1-KB loads per wave), then float [W2P_UNITS * 4 + nt * 64 + lane] = the lane's
-// channel's 1 / scale.
-constexpr int W2P_UNITS = 4 * 18 * 64;
-constexpr int W2P_FLOATS = W2P_UNITS * 4 + 4 * 64;
-__global__ __launch_bounds__(64) void c4_w2_planes_kernel(const float* __restrict__ w2,
-                                                          float* __restrict__ out) {
-  const int nt = blockIdx.x, lane = threadIdx.x;
-  const int co = 16 * nt + (lane & 15), h = lane >> 4;
-  float breg[72];
-#pragma unroll
-  for (int st = 0; st < 72; ++st) breg[st] = w2[co * 288 + (8 * h + (st & 7)) * 9 + (st >> 3)];
-  bf16x8 bh[9], bl[9];
-  const float iw = w2_planes(breg, bh, bl);
-  u32x4* const u = reinterpret_cast<u32x4*>(out);
-#pragma unroll
-  for (int t = 0; t < 9; ++t) {
-    u[(nt * 18 + t) * 64 + lane] = __builtin_bit_cast(u32x4, bh[t]);
-    u[(nt * 18 + 9 + t) * 64 + lane] = __builtin_bit_cast(u32x4, bl[t]);
-  }
-  out[W2P_UNITS * 4 + nt * 64 + lane] = iw;
-}
-
-// conv2_planes: the fragment planes of registered conv2 weights, cached per weight generation
-// like w_planes (double buffer, the recompute synchronises its stream before publishing);
-// nullptr for unregistered weights or when memory is short (the trunk then stages the weights
-// through LDS and splits them itself: the same planes, the same bits).
-const float* conv2_planes(const float* w2, hipStream_t s) {
-  if (!weights_registered(w2, 64, 288, 288)) return nullptr;
-  const long gen = g_wgen.load();
-  std::lock_guard<std::mutex> lk(g_wmu);
-  WScaleEntry* e = wcache_entry(w2, 64, 288, 288);
-  if (!e) return nullptr;
-  if (!e->frags[0]) {
-    if (hipMalloc(&e->frags[0], (size_t)2 * W2P_FLOATS * sizeof(float)) != hipSuccess) {
-      e->frags[0] = nullptr;
-      return nullptr;
-    }
-    e->frags[1] = e->frags[0] + W2P_FLOATS;
-    e->fgen = 0;
-  }
-  if (e->fgen == gen) return e->frags[e->fcur];
-  const int nxt = e->fcur ^ 1;
-  hipLaunchKernelGGL(c4_w2_planes_kernel, dim3(4), dim3(64), 0, s, w2, e->frags[nxt]);
-  if (hipStreamSynchronize(s) != hipSuccess) return nullptr;
-  e->fcur = nxt;
-  e->fgen = gen;
-  return e->frags[nxt];
-}
-
-// The heads composed with the Linear in front of them (output_transform.2 -> fc_policy /
-// fc_value, no nonlinearity between: Connect4GNN.py:106-114, gnn_utils.py:115):
-//   out[a][k] = sum_j Wh[a][j] W2[j][k]   (rows 0..A-1: fc_policy, row A: fc_value)
-//   out[(A + 1) F + a] = sum_j Wh[a][j] b2[j] + bh[a]
-// accumulated in fp64 from the fp32 inputs (each product is exact) and rounded once to fp32.
-// W2 (39 MB at F = 3136) is read once, row-major, by the whole chip: block (x, y) owns columns
-// 64 x .. 64 x + 63 (lane = column, coalesced rows of W2) and the y-th of COMPOSE_JB row ranges;
-// wave g of its 16 sums the range's 4-row groups g, g + 16, ... in row order (the groups' head
-// weights are wave-uniform 16-byte loads), the 16 wave sums are added in wave order through LDS
-// and leave as fp64 partials part[y][9][F] (slot 8: the value row); compose_heads_sum_kernel adds
-// the COMPOSE_JB partials in order and rounds.  A fixed summation order, no atomics.  Block
-// (ceil(F / 64), 0) forms the composed biases the same way over 256 strided partial sums.
-constexpr int COMPOSE_JB = 4;
-__global__ __launch_bounds__(1024) void compose_heads_kernel(
-    const float* __restrict__ w2, const float* __restrict__ b2, const float* __restrict__ wp,
-    const float* __restrict__ bp, const float* __restrict__ wv, const float* __restrict__ bv,
-    int F, int A, double* __restrict__ part, float* __restrict__ out) {
-  __shared__ double sh[3][16][64];
-  const int lane = threadIdx.x & 63;
-  const int g = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if ((int)blockIdx.x == (F + 63) / 64) {       // the biases: bc = Wh b2 + bh
-    if (blockIdx.y != 0) return;
-    double* ps = &sh[0][0][0];                  // [9][256] partial sums, then [9][16]
-    double* ps2 = ps + 9 * 256;
-    const int t = threadIdx.x;
-    if (t < 256) {
-      double acc[9];
-#pragma unroll
-      for (int a = 0; a < 9; ++a) acc[a] = 0.0;
-      for (int j = t; j < F; j += 256) {
-        const double b = (double)b2[j];
-#pragma unroll
-        for (int a = 0; a < 8; ++a)
-          if (a < A) acc[a] += (double)wp[(size_t)a * F + j] * b;
-        acc[8] += (double)wv[j] * b;
-      }
-#pragma unroll
-      for (int a = 0; a < 9; ++a) ps[a * 256 + t] = acc[a];
-    }
-    __syncthreads();
-    if (t < 9 * 16) {
-      const int a = t >> 4, q = t & 15;
-      double s = 0.0;
-      for (int i = 0; i < 16; ++i) s += ps[a * 256 + q * 16 + i];
-      ps2[a * 16 + q] = s;
-    }
-    __syncthreads();
-    if (t < 9 && (t < A || t == 8)) {
-      double s = 0.0;
-      for (int q = 0; q < 16; ++q) s += ps2[t * 16 + q];
-      const int row = t == 8 ? A : t;
-      out[(size_t)(A + 1) * F + row] = (float)(s + (double)(t == 8 ? bv[0] : bp[t]));
-    }
-    return;
-  }
-  const int k = blockIdx.x * 64 + lane;
-  const bool kin = k < F;
-  const int kc = kin ? k : F - 1;
-  double acc[9];
-#pragma unroll
-  for (int a = 0; a < 9; ++a) acc[a] = 0.0;
-  // the range's rows (a multiple of 4, as F is): two 4-row groups per pass, 8 rows in flight
-  const int JR = ((F + COMPOSE_JB - 1) / COMPOSE_JB + 3) & ~3;
-  const int j0 = blockIdx.y * JR, j1 = min(F, j0 + JR);
-  auto add4 = [&](int j, const float (&x)[4]) {
-    f32x4 wh[9];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-      wh[a] = *reinterpret_cast<const f32x4*>(wp + (size_t)min(a, A - 1) * F + j);
-    wh[8] = *reinterpret_cast<const f32x4*>(wv + j);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const double xd = (double)x[u];
-#pragma unroll
-      for (int a = 0; a < 8; ++a)
-        if (a < A) acc[a] += (double)wh[a][u] * xd;
-      acc[8] += (double)wh[8][u] * xd;
-    }
-  };
-  for (int j = j0 + 4 * g; j < j1; j += 128) {
-    const bool two = j + 64 < j1;
-    const int jb = two ? j + 64 : j;
-    float xa[4], xb[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) xa[u] = w2[(size_t)(j + u) * F + kc];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) xb[u] = w2[(size_t)(jb + u) * F + kc];
-    add4(j, xa);
-    if (two) add4(jb, xb);
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 3; ++i) sh[i][g][lane] = acc[3 * r + i];
-    __syncthreads();
-    if (threadIdx.x < 192) {
-      const int i = threadIdx.x >> 6, a = 3 * r + i;
-      double s = 0.0;
-      for (int q = 0; q < 16; ++q) s += sh[i][q][lane];
-      if (kin && (a < A || a == 8)) part[((size_t)blockIdx.y * 9 + a) * F + k] = s;
-    }
-  }
-}
-
-// Wc = the COMPOSE_JB partials of compose_heads_kernel added in range order, rounded to fp32
-__global__ __launch_bounds__(256) void compose_heads_sum_kernel(const double* __restrict__ part,
-                                                                int F, int A,
-                                                                float* __restrict__ out) {
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= 9 * F) return;
-  const int a = idx / F, k = idx - a * F;
-  if (a >= A && a != 8) return;
-  double s = 0.0;
-#pragma unroll
-  for (int y = 0; y < COMPOSE_JB; ++y) s += part[((size_t)y * 9 + a) * F + k];
-  out[(size_t)(a == 8 ? A : a) * F + k] = (float)s;
-}
-
-// Floats of Wc [A + 1][F] + bc [A + 1], and the bytes composing them needs: that, then the fp64
-// partials [COMPOSE_JB][9][F]
-size_t composed_heads_floats(int F, int A) { return (size_t)(A + 1) * F + (size_t)(A + 1); }
-static size_t composed_out_bytes(int F, int A) {
-  return (composed_heads_floats(F, A) * sizeof(float) + 255) / 256 * 256;
-}
-size_t composed_heads_scratch_bytes(int F, int A) {
-  return composed_out_bytes(F, A) + (size_t)COMPOSE_JB * 9 * F * sizeof(double);
-}
-
-static int launch_compose(const float* w2, const float* b2, const float* wp, const float* bp,
-                          const float* wv, const float* bv, int F, int A, float* out,
-                          double* part, hipStream_t s) {
-  hipLaunchKernelGGL(compose_heads_kernel, dim3((F + 63) / 64 + 1, COMPOSE_JB), dim3(1024), 0, s,
-                     w2, b2, wp, bp, wv, bv, F, A, part, out);
-  hipLaunchKernelGGL(compose_heads_sum_kernel, dim3((9 * F + 255) / 256), dim3(256), 0, s, part, F,
-                     A, out);
-  return check_launch("compose_heads_kernel");
-}
-
-// Wc [A + 1][F] followed by bc [A + 1] for heads (wp, bp, wv, bv) behind y = x W2^T + b2
-// (A <= 8, F % 4 == 0, wp / wv 16-byte aligned): the cached copy when every input is registered,
-// else composed into `scratch` (composed_heads_scratch_bytes(F, A) bytes of the caller's
-// workspace, 256-byte aligned) on the caller's stream -- the same kernels either way, so the
-// same bits.  nullptr: a launch failed.
-
-const float* composed_heads(const float* w2, const float* b2, const float* wp, const float* bp,
-                            const float* wv, const float* bv, int F, int A, float* scratch,
-                            hipStream_t s) {
-  const bool reg = weights_registered(w2, F, F, F) && weights_registered(b2, 1, F, F) &&
-                   weights_registered(wp, A, F, F) && weights_registered(bp, 1, A, A) &&
-                   weights_registered(wv, 1, F, F) && weights_registered(bv, 1, 1, 1);
-  if (reg) {
-    const long gen = g_wgen.load();
-    std::lock_guard<std::mutex> lk(g_wmu);
-    ComposedEntry* e = nullptr;
-    for (auto& x : g_ccache)
-      if (x.in[0] == w2 && x.in[1] == b2 && x.in[2] == wp && x.in[3] == bp && x.in[4] == wv &&
-          x.in[5] == bv && x.F == F && x.A == A)
-        e = &x;
-    if (!e) {
-      // one allocation: the two Wc / bc buffers, then the partials (used only while a recompute
-      // runs, which ends before g_wmu is released)
-      ComposedEntry x{{w2, b2, wp, bp, wv, bv}, F, A, {nullptr, nullptr}, nullptr, 1, 0};
-      const size_t one = composed_out_bytes(F, A);
-      char* base = nullptr;
-      if (hipMalloc(&base, one + composed_heads_scratch_bytes(F, A)) == hipSuccess) {
-        x.buf[0] = reinterpret_cast<float*>(base);
-        x.buf[1] = reinterpret_cast<float*>(base + one);
-        x.part = reinterpret_cast<double*>(base + 2 * one);
-        g_ccache.push_back(x);
-        e = &g_ccache.back();
-      }
-    }
-    if (e) {
-      if (e->gen == gen) return e->buf[e->cur];
-      const int nxt = e->cur ^ 1;
-      if (launch_compose(w2, b2, wp, bp, wv, bv, F, A, e->buf[nxt], e->part, s) ||
-          hipStreamSynchronize(s) != hipSuccess)
-        return nullptr;
-      e->cur = nxt;
-      e->gen = gen;
-      return e->buf[nxt];
-    }
-  }
-  double* part = reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) +
-                                           composed_out_bytes(F, A));
-  return launch_compose(w2, b2, wp, bp, wv, bv, F, A, scratch, part, s) ? nullptr : scratch;
-}
-
 // the split-K HEADS tiles' finalize (P = 128-column tiles x k splits)
 static void launch_heads_finalize(GemmArgs& a, hipStream_t s) {
   const int P = (a.N + 127) / 128 * a.splits;
@@ -4332,13 +2901,26 @@ static void launch_heads_finalize(GemmArgs& a, hipStream_t s) {
   a.heads_done = 1;
 }
 
+// AZ_GEMM_X3 (tuning build): 0 = keep the fp32 MFMA tiles, 1 / 2 = force the 256x128 / 128x128
+// gemm_x3 tile; -1 when unset, and for any other value
+static int x3_env_tile() {
+  static const int v = [] {
+    const char* e = tuning_env("AZ_GEMM_X3");
+    const int t = e ? atoi(e) : -1;
+    return t >= 0 && t <= 2 ? t : -1;
+  }();
+  return v;
+}
+
 // gemm_x3 launch for a K-major A and W (no A2 / gathered rows), M > 64: 256x128 (8 waves) above
 // M = 256, else 128x128 (4 waves); split-K so the grid nears one block per CU (measured on
 // MI355X, tools/gemm_sweep.py x3: M = 512 75 us vs 103 us for the fp32 MFMA tile, M = 800 147 vs
-// 185, M = 4096 516 vs 767).  Tuning build: AZ_GEMM_X3=0 keeps the fp32 MFMA tiles, 1..4 forces
-// a tile, AZ_GEMM_SPLITS the split.  Sets a.splits / a.kc; false = not launched.
+// 185, M = 4096 516 vs 767).  Tuning build: AZ_GEMM_X3=0 keeps the fp32 MFMA tiles, 1 / 2 forces
+// the 256x128 / 128x128 tile, AZ_GEMM_SPLITS the split.  Sets a.splits / a.kc; false = not
+// launched.
 static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSplitA* pre) {
-  static const char* env = tuning_env("AZ_GEMM_X3");
+  const int env_tile = x3_env_tile();
+  const bool env = env_tile >= 0;
   static const char* env_split = tuning_env("AZ_GEMM_SPLITS");
   // the fp16 form (H3) for the product tiles when the workspace can hold A's row scales (taken
   // from its end, after every split-K slab); tuning build: AZ_GEMM_PREC=x3 keeps the bf16 form
@@ -4359,7 +2941,7 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
   // reduce of the layer before) needs no room for them here
   const bool have_pre = pre && pre->planes && pre->sc && aligned16(pre->planes);
   const size_t p2a_bytes = have_pre ? 0 : ((size_t)4 * a.M * a.K + 255) / 256 * 256;
-  bool p2 = h3 && !tuning_env("AZ_GEMM_X3") && !tuning_env("AZ_GEMM_SPLITS") &&
+  bool p2 = h3 && !env && !tuning_env("AZ_GEMM_SPLITS") &&
             !tuning_env("AZ_GEMM_NOP2") && whole_k && a.lda % 4 == 0 && a.ldb % 4 == 0 &&
             aligned16(a.A) && aligned16(a.B) && ws_bytes >= p2a_bytes + 256 &&
             weights_registered(a.B, a.N, a.K, a.ldb);
@@ -4376,8 +2958,7 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
       a.apl = pre->planes;
       a.sa = pre->sc;
     } else {
-      hipLaunchKernelGGL(h3_split_rows_kernel, dim3(a.M), dim3(256), 0, s, a.A, a.M, a.K, a.lda,
-                         H3_TA, apl_buf, sa_buf);
+      launch_h3_split_rows(a.A, a.M, a.K, a.lda, H3_TA, apl_buf, sa_buf, s);
       a.apl = apl_buf;
       a.sa = sa_buf;
     }
@@ -4391,26 +2972,18 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
   auto h3_scales = [&]() {
     const float* sw = w_row_scales(a.B, a.N, a.K, a.ldb, s);
     if (!sw) {                          // not cacheable: this call's own W scales
-      hipLaunchKernelGGL(row_scale_kernel, dim3(a.N), dim3(256), 0, s, a.B, a.N, a.K, a.ldb,
-                         H3_TW, sw_buf);
+      launch_row_scale(a.B, a.N, a.K, a.ldb, H3_TW, sw_buf, s);
       sw = sw_buf;
     }
-    hipLaunchKernelGGL(row_scale_kernel, dim3(a.M), dim3(256), 0, s, a.A, a.M, a.K,
-                       a.lda, H3_TA, sa_buf);
+    launch_row_scale(a.A, a.M, a.K, a.lda, H3_TA, sa_buf, s);
     a.sa = sa_buf;
     a.sw = sw;
     return true;
   };
-  int tile = env ? atoi(env) : 0;
-  if (env && tile == 0) return false;
+  if (env_tile == 0) return false;
   if (!env && a.M <= 64) return false;  // tools/gemm_sweep.py x3: fp32 tiles win to M = 64 (27 vs 31 us)
-  // 7..11: gemm_x3<256,128> timing ablations (ABL 1, 2, 4, 5, 3), K % 32 == 0 only
-  const int bms[17] = {0, 256, 128, 128, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256, 256};
-  const int bns[17] = {0, 128, 128, 64, 128, 128, 128, 128, 128, 128, 128, 128, 128, 128, 128, 128, 128};
-  if (tile < 1 || tile > 16 || (((tile >= 7 && tile <= 11) || tile >= 13) && a.K % 32 != 0)) {
-    tile = a.M > 256 ? 1 : 2;
-  }
-  const int bm = bms[tile], bn = bns[tile];
+  const int tile = env ? env_tile : a.M > 256 ? 1 : 2;   // 1: 256x128 (8 waves), 2: 128x128 (4)
+  const int bm = tile == 1 ? 256 : 128, bn = 128;
   const long tiles = (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
   int S = 1;
   if (env_split) {
@@ -4424,10 +2997,10 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
   if (S > 1) a.splits = (a.K + a.kc - 1) / a.kc;
   const dim3 grid((unsigned)(tiles * a.splits));
   const bool whole = a.K % 32 == 0;   // kc is a multiple of 32 too: no partial k tile anywhere
-  // Stream-K (gemm_x3_sk) for the 256 x 128 tile when the split-K grid leaves CUs idle (below
-  // 90 % of its last round: M = 800 -> 200 blocks, M = 1,576 -> 175): one block per CU, equal
-  // k-iteration ranges, split tiles summed by streamk_fixup4_kernel.  C is complete on return
-  // (a.splits = 1).  Product dispatch only (the tuning overrides keep the split-K forms).
+  // Stream-K (gemm_x3_csk) for the 256 x 128 tile when the split-K grid leaves CUs idle (below
+  // 90 % of its last round: M = 800 -> 200 blocks, M = 1,576 -> 175): equal k-iteration ranges,
+  // split tiles summed by csk_fixup4_kernel.  C is complete on return (a.splits = 1).  Product
+  // dispatch only (the tuning overrides keep the split-K forms).
   if (!env && !env_split && tile == 1 && a.vec_epi && a.slab && tiles >= 64) {
     static int cus = 0;
     if (cus <= 0) {
@@ -4443,9 +3016,9 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
     const int B = (int)std::min<long>(cus, I);
     const long per = I / B;
     if ((double)blocks / (double)(rounds * cus) < 0.9 && per >= 8) {
-      // cycled stream-K (gemm_x3_csk).  Tuning build: AZ_CSK = "off" runs round 3's gemm_x3_sk,
-      // "am,an,bf,at,bt" forces a plan (csk_make), AZ_CSK_MISS sets the planner's miss cost,
-      // AZ_CSK_PRINT prints the plan
+      // cycled stream-K (gemm_x3_csk).  Tuning build: AZ_CSK = "off" keeps the split-K tiles
+      // below, "am,an,bf,at,bt" forces a plan (csk_make), AZ_CSK_MISS sets the planner's miss
+      // cost, AZ_CSK_PRINT prints the plan
       CskPlan cq{};
       bool use_csk = true, ok = false;
 #ifdef AZ_TUNING
@@ -4467,12 +3040,6 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
       ok = csk_plan_cached(a.M, a.N, a.K, cus, CSK_MISS_COST, cq);
 #endif
       const int mp = use_csk && ok ? csk_max_pieces(cq) : 0;
-#ifdef AZ_TUNING
-      static const char* env_cring = tuning_env("AZ_P3_RING");
-      const int csk_ring = env_cring ? atoi(env_cring) : 3;
-#else
-      constexpr int csk_ring = 3;
-#endif
       // the finalize gives each lane one whole 64-column block of a row: N % 64 == 0, N <= 4,096
       if (use_csk && ok && a.he.part && whole && (p2 || h3) && a.N % 64 == 0 && a.N <= 64 * 64 &&
           (size_t)a.M * (a.N / 64) * mp * HEADS_TILE_SLOTS * 4 * 2 <= ws_bytes &&
@@ -4481,9 +3048,7 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
         if (p2) p2 = p2_prep();
         if (!p2) h3 = h3_scales();
         a.he.mp = mp;
-        if (p2 && csk_ring == 2)
-          hipLaunchKernelGGL((gemm_x3_csk<false, true, true, true, 2>), dim3(cq.B), dim3(512), 0, s, a, cq);
-        else if (p2) hipLaunchKernelGGL((gemm_x3_csk<false, true, true, true>), dim3(cq.B), dim3(512), 0, s, a, cq);
+        if (p2) hipLaunchKernelGGL((gemm_x3_csk<false, true, true, true>), dim3(cq.B), dim3(512), 0, s, a, cq);
         else hipLaunchKernelGGL((gemm_x3_csk<false, true, false, true>), dim3(cq.B), dim3(512), 0, s, a, cq);
         const int P = (a.N / 64) * mp;
         hipLaunchKernelGGL(heads_tiles_finalize_kernel<true>, dim3((a.M + 3) / 4), dim3(256),
@@ -4496,9 +3061,7 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
       if (use_csk && ok && mp * (size_t)a.M * a.N * 4 <= ws_bytes) {
         if (p2) p2 = p2_prep();
         if (!p2 && h3) h3 = h3_scales();
-        if (p2 && csk_ring == 2)
-          hipLaunchKernelGGL((gemm_x3_csk<false, true, true, false, 2>), dim3(cq.B), dim3(512), 0, s, a, cq);
-        else if (p2) hipLaunchKernelGGL((gemm_x3_csk<false, true, true>), dim3(cq.B), dim3(512), 0, s, a, cq);
+        if (p2) hipLaunchKernelGGL((gemm_x3_csk<false, true, true>), dim3(cq.B), dim3(512), 0, s, a, cq);
         else if (h3 && whole) hipLaunchKernelGGL((gemm_x3_csk<false, true>), dim3(cq.B), dim3(512), 0, s, a, cq);
         else if (h3) hipLaunchKernelGGL((gemm_x3_csk<true, true>), dim3(cq.B), dim3(512), 0, s, a, cq);
         else if (whole) hipLaunchKernelGGL((gemm_x3_csk<false, false>), dim3(cq.B), dim3(512), 0, s, a, cq);
@@ -4509,108 +3072,36 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
         a.splits = 1;
         return true;
       }
-#ifdef AZ_TUNING
-      const SkPlan q = sk_plan(a.M, a.N, a.K, 256, 128, B, false);
-      if ((size_t)sk_max_pieces(q, a.N, 128) * a.M * a.N * 4 <= ws_bytes) {
-        if (whole) hipLaunchKernelGGL((gemm_x3_sk<256, 128, 4, 2, false>), dim3(B), dim3(512), 0, s, a, q);
-        else hipLaunchKernelGGL((gemm_x3_sk<256, 128, 4, 2, true>), dim3(B), dim3(512), 0, s, a, q);
-        const long n4 = (long)a.M * (a.N / 4);
-        hipLaunchKernelGGL(streamk_fixup4_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0,
-                           s, a, 256, 128, q);
-        a.splits = 1;
-        return true;
-      }
-#endif
     }
   }
-#ifdef AZ_TUNING
-  // A split once into bf16 planes (x3_split_kernel) in the workspace after the slabs, only W
-  // split in the tile (AZ_GEMM_X3APL=1): measured slower -- M = 512 82.8 vs 75.0 us incl. the
-  // split launch, M = 4096 557 vs 514 (1.5x the A bytes through L2, no clock gain)
-  static const char* env_apl = tuning_env("AZ_GEMM_X3APL");
-  const bool want_apl = env_apl && atoi(env_apl) != 0;
-  const size_t slab_bytes = a.splits > 1 ? ((size_t)a.splits * a.M * a.N * 4 + 255) / 256 * 256 : 0;
-  const size_t apl_bytes = (size_t)3 * a.M * a.K * 2;
-  if (want_apl && tile == 1 && whole && a.lda % 4 == 0 && a.slab &&
-      slab_bytes + apl_bytes <= ws_bytes) {
-    unsigned short* pl = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(a.slab) + slab_bytes);
-    const long segs = (long)a.M * (a.K / 8);
-    hipLaunchKernelGGL(x3_split_kernel, dim3((unsigned)((segs + 255) / 256)), dim3(256), 0, s,
-                       a.A, a.lda, a.M, a.K, pl, (size_t)a.M * a.K);
-    a.apl = pl;
-    a.apl_plane = (size_t)a.M * a.K;
-    hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 0, true>), grid, dim3(512), 0, s, a);
-    return true;
-  }
-#endif
 #define AZ_X3(BM_, BN_, WM_, WN_)                                                              \
   if (whole) hipLaunchKernelGGL((gemm_x3<BM_, BN_, WM_, WN_, false>), grid, dim3(64 * WM_ * WN_), \
                                 0, s, a);                                                      \
   else hipLaunchKernelGGL((gemm_x3<BM_, BN_, WM_, WN_, true>), grid, dim3(64 * WM_ * WN_), 0, s, a);
 #define AZ_H3(BM_, BN_, WM_, WN_)                                                              \
-  if (whole) hipLaunchKernelGGL((gemm_x3<BM_, BN_, WM_, WN_, false, 0, false, 32, true>), grid,  \
+  if (whole) hipLaunchKernelGGL((gemm_x3<BM_, BN_, WM_, WN_, false, true>), grid,                \
                                 dim3(64 * WM_ * WN_), 0, s, a);                                \
-  else hipLaunchKernelGGL((gemm_x3<BM_, BN_, WM_, WN_, true, 0, false, 32, true>), grid,         \
-                          dim3(64 * WM_ * WN_), 0, s, a);
-  if (p2 && (tile == 1 || tile == 2) && p2_prep()) {
-    // the 256 x 128 tile's LDS-DMA ring: 3 stages (two in flight) in the product; the tuning
-    // build's AZ_P3_RING=2 keeps round 5's double buffer for A/B runs (same bits)
-    static const char* env_ring = tuning_env("AZ_P3_RING");
-    const int ring = env_ring ? atoi(env_ring) : 3;
-    static const char* env_abl = tuning_env("AZ_P3_ABL");
-    const int abl = env_abl ? atoi(env_abl) : 0;
-    if (false) {
-    }
-#ifdef AZ_TUNING
-    else if (tile == 1 && abl == 1)
-      hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 3, 1>), grid, dim3(512), 0, s, a);
-    else if (tile == 1 && abl == 2)
-      hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 3, 2>), grid, dim3(512), 0, s, a);
-    else if (tile == 1 && abl == 4)
-      hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 3, 4>), grid, dim3(512), 0, s, a);
-    else if (tile == 1 && abl == 5)
-      hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 3, 5>), grid, dim3(512), 0, s, a);
-    else if (tile == 1 && abl == 6)
-      hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 3, 6>), grid, dim3(512), 0, s, a);
-    else if (tile == 1 && tuning_env("AZ_P3_WIDE")) {
-      // 256 x 256 tiles (waves 4 x 2 of 64 x 128): 2/3 of the 256 x 128 tile's DMA bytes per
-      // flop; AZ_P3_WIDE_SPLITS = its split-K (default: none)
-      static const char* env_ws = tuning_env("AZ_P3_WIDE_SPLITS");
-      int S = env_ws ? atoi(env_ws) : 1;
-      while (S > 1 && (!a.slab || (size_t)S * a.M * a.N * 4 > ws_bytes)) --S;
-      a.kc = S > 1 ? ((a.K + S - 1) / S + 31) / 32 * 32 : a.K;
-      a.splits = S > 1 ? (a.K + a.kc - 1) / a.kc : 1;
-      const dim3 gw((unsigned)(((a.M + 255) / 256) * ((a.N + 255) / 256) * a.splits));
-      hipLaunchKernelGGL((gemm_p3<256, 256, 4, 2, true>), gw, dim3(512), 0, s, a);
-    }
-    else if (tile == 1 && ring == 2) {
-      if (a.he.part) {
-        hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 2, 0, true>), grid, dim3(512), 0, s, a);
-        launch_heads_finalize(a, s);
-      } else {
-        hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 2>), grid, dim3(512), 0, s, a);
-      }
-    }
-#endif
-    else if (a.he.part) {
+  else hipLaunchKernelGGL((gemm_x3<BM_, BN_, WM_, WN_, true, true>), grid, dim3(64 * WM_ * WN_), \
+                          0, s, a);
+  if (p2 && p2_prep()) {
+    // the 256 x 128 tile's LDS-DMA ring has 3 stages (two in flight), the 128 x 128 tile's 2
+    if (a.he.part) {
       if (tile == 1)
-        hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 3, 0, true>), grid, dim3(512), 0, s, a);
+        hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 3, true>), grid, dim3(512), 0, s, a);
       else
-        hipLaunchKernelGGL((gemm_p3<128, 128, 2, 2, true, 2, 0, true>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((gemm_p3<128, 128, 2, 2, true, 2, true>), grid, dim3(256), 0, s, a);
       launch_heads_finalize(a, s);
     }
     else if (tile == 1) hipLaunchKernelGGL((gemm_p3<256, 128, 4, 2, true, 3>), grid, dim3(512), 0, s, a);
     else hipLaunchKernelGGL((gemm_p3<128, 128, 2, 2, true>), grid, dim3(256), 0, s, a);
     return true;
   }
-  if (h3 && (tile == 1 || tile == 2) && h3_scales()) {
+  if (h3 && h3_scales()) {
     if (a.he.part && whole) {     // the heads from the tiles, as on the P2 tiles (same bits)
       if (tile == 1)
-        hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 0, false, 32, true, true>), grid,
-                           dim3(512), 0, s, a);
+        hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, true, true>), grid, dim3(512), 0, s, a);
       else
-        hipLaunchKernelGGL((gemm_x3<128, 128, 2, 2, false, 0, false, 32, true, true>), grid,
-                           dim3(256), 0, s, a);
+        hipLaunchKernelGGL((gemm_x3<128, 128, 2, 2, false, true, true>), grid, dim3(256), 0, s, a);
       launch_heads_finalize(a, s);
       return true;
     }
@@ -4618,38 +3109,10 @@ static bool launch_x3(GemmArgs& a, size_t ws_bytes, hipStream_t s, const PreSpli
     else { AZ_H3(128, 128, 2, 2) }
     return true;
   }
-  switch (tile) {
-    case 1: AZ_X3(256, 128, 4, 2) break;
-#ifdef AZ_TUNING
-    case 3: AZ_X3(128, 64, 2, 1) break;
-    case 4: AZ_X3(256, 128, 2, 2) break;
-    // wave-specialised x3 (measured no faster: M = 512 84 vs 78 us, M = 4096 541 vs 518)
-    case 5:
-      if (whole) hipLaunchKernelGGL((gemm_x3ws<256, 128, 4, 2, false>), grid, dim3(768), 0, s, a);
-      else hipLaunchKernelGGL((gemm_x3ws<256, 128, 4, 2, true>), grid, dim3(768), 0, s, a);
-      break;
-    case 12:
-      if (whole) hipLaunchKernelGGL((gemm_x3pp<256, 128, false>), grid, dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((gemm_x3pp<256, 128, true>), grid, dim3(512), 0, s, a);
-      break;
-    case 7: hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 1>), grid, dim3(512), 0, s, a); break;
-    case 8: hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 2>), grid, dim3(512), 0, s, a); break;
-    case 9: hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 4>), grid, dim3(512), 0, s, a); break;
-    case 10: hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 5>), grid, dim3(512), 0, s, a); break;
-    case 11: hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 3>), grid, dim3(512), 0, s, a); break;
-    case 13: hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 8>), grid, dim3(512), 0, s, a); break;
-    case 14:   // 16x16x32 MFMA blocks
-      if (whole) hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, false, 0, false, 16>), grid, dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((gemm_x3<256, 128, 4, 2, true, 0, false, 16>), grid, dim3(512), 0, s, a);
-      break;
-    case 6:   // 4 consumer waves with 128 x 64 wave tiles (two waves per SIMD)
-      if (whole) hipLaunchKernelGGL((gemm_x3ws<256, 128, 2, 2, false>), grid, dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((gemm_x3ws<256, 128, 2, 2, true>), grid, dim3(512), 0, s, a);
-      break;
-#endif
-    default: AZ_X3(128, 128, 2, 2) break;
-  }
+  if (tile == 1) { AZ_X3(256, 128, 4, 2) }
+  else { AZ_X3(128, 128, 2, 2) }
 #undef AZ_X3
+#undef AZ_H3
   return true;
 }
 
@@ -4715,18 +3178,6 @@ int gemm_f32_partial(const az_gemm_desc* d, hipStream_t s, int* splits_out, cons
     return check_launch("gemv_f32");
   }
   if (akm && bkm && launch_tall(a, s)) return check_launch("gemm_tall");
-  // gemm_kslice: measured slower than the split-K tile so far (111 vs 103 us at M = 512), so
-  // only the tuning build runs it, on request (AZ_GEMM_KSLICE=1, tools/gemm_sweep.py kslice)
-  static const bool use_kslice = tuning_env("AZ_GEMM_KSLICE") != nullptr;
-  if (akm && bkm && use_kslice && !d->A2 && !d->a_rows && !d->b_rows && !d->C2 && !d->R &&
-      !d->G && d->beta == 0.f && d->act != AZ_ACT_DRELU && aligned16(d->A) && aligned16(d->B)) {
-    const int nn = kslice_narrow(a);
-    if (nn >= 0) {
-      const dim3 grid(a.M / 32 * 16);
-      hipLaunchKernelGGL((gemm_kslice<7, 6>), grid, dim3(512), 0, s, a, nn);
-      return check_launch("gemm_kslice");
-    }
-  }
   const bool glds_ok = akm && bkm && !d->A2 && !d->a_rows;
   // the heads from the tiles (az_x3.h HeadsEpi): only a plain y = x W^T + b, whole 32-column
   // chunks, A <= 8; launch_x3 takes it on its P2 split-K tiles and says so in a.heads_done
@@ -4739,37 +3190,32 @@ int gemm_f32_partial(const az_gemm_desc* d, hipStream_t s, int* splits_out, cons
     return check_launch("gemm_x3");
   }
   a.he = HeadsEpi{};
-  // tile choice (tuning override for experiments: AZ_GEMM_CFG=<index into kCfgs>)
-  static const char* env_cfg = tuning_env("AZ_GEMM_CFG");
-  int cfg = 0;
+  // tile choice
+  Tile cfg;
   int s256 = 0;   // split factor when the 256x128 8-wave tile packs the chip (one block per CU)
-  if (env_cfg) {
-    cfg = std::min(std::max(atoi(env_cfg), 0), kNumCfgs - 1);
-    if (cfg >= 6 && !glds_ok) cfg = 0;
-  } else if (glds_ok && d->M > 256 && (s256 = splits_256x128(d->M, d->N, d->K, d->ws_bytes)) > 0) {
+  if (glds_ok && d->M > 256 && (s256 = splits_256x128(d->M, d->N, d->K, d->ws_bytes)) > 0) {
     // 256x128 tile, 8 waves, one block per CU, K split so the grid fills >= 85 % of the CUs
-    // (tools/gemm_sweep.py glds on MI355X, M = 512: 106 us vs 113 us for 128x128 x 5)
-    cfg = 24;
+    // (M = 512 on MI355X: 106 us vs 113 us for 128x128 x 5)
+    cfg = TILE_GLDS2_256x128;
   } else if (glds_ok && d->N >= 1024 && d->K >= 1024 && full_waves_256x128(d->M, d->N)) {
     // large M whose 256x128 grid is (nearly) whole rounds of 256 blocks: the 8-wave tile's
-    // steady state wins (tools/gemm_sweep.py bigm, M = 65,536: 130 vs 109 TFLOP/s for 128x64)
-    cfg = 24;
+    // steady state wins (M = 65,536: 130 vs 109 TFLOP/s for 128x64)
+    cfg = TILE_GLDS2_256x128;
   } else if (glds_ok && d->M > 128) {
-    // LDS-DMA tiles (tools/gemm_sweep.py glds on MI355X): 128x64 once the grid fills the chip,
-    // 128x128 + split-K below that
+    // LDS-DMA tiles: 128x64 once the grid fills the chip, 128x128 + split-K below that
     const long t128 = (long)((d->M + 127) / 128) * ((d->N + 127) / 128);
-    cfg = t128 >= 256 ? 8 : 6;
+    cfg = t128 >= 256 ? TILE_GLDS_128x64 : TILE_GLDS_128x128;
   } else {
-    cfg = 0;  // register-staged 64x64x32: gathered / concatenated operands, small M
+    cfg = TILE_REG_64x64;   // gathered / concatenated operands, small M
   }
   static const char* env_ring = tuning_env("AZ_GEMM_RING");   // experiment: 3-buffer 256x128
-  if (cfg == 24 && env_ring) {
+  if (cfg == TILE_GLDS2_256x128 && env_ring) {
     const int r = atoi(env_ring);
-    cfg = r == 3 ? 29 : r == 4 ? 31 : r == 5 ? 30 : r == 6 ? 32 : 24;
+    cfg = r == 3 ? TILE_RING_256x128 : r == 4 ? TILE_RING_ST_256x128 : TILE_GLDS2_256x128;
   }
   const TileCfg& tc = kCfgs[cfg];
   plan(a, tc.bm, tc.bn, tc.bk, d->ws_bytes);
-  const bool is128 = tc.bm == 128 && tc.bn == 128 && cfg >= 6;
+  const bool is128 = cfg == TILE_GLDS_128x128;
   if (s256 > 0 && !tuning_env("AZ_GEMM_SPLITS")) {
     a.splits = s256;
     a.kc = s256 > 1 ? ((a.K + s256 - 1) / s256 + 31) / 32 * 32 : a.K;
@@ -4822,36 +3268,6 @@ int splitk_reduce(const az_gemm_desc* d, int splits, hipStream_t s) {
   return check_launch("splitk_reduce_kernel");
 }
 
-// splitk_reduce, and C's rows split for a P2 GEMM that takes C as its A (PreSplitA{planes, sc}:
-// planes [2][M][N] fp16, sc [2][M]); C's bits are splitk_reduce's.  Returns 1 when launched, 0 when
-// the shapes / epilogue do not qualify (nothing launched: the caller reduces the usual way), or a
-// negative AZ_E* code.
-int splitk_reduce_split(const az_gemm_desc* d, int splits, unsigned short* planes, float* sc,
-                        hipStream_t s, bool write_c) {
-  if (!(splits >= 2 && splits <= 8 && d->N % 32 == 0 && d->N <= 4096 && d->M > 0 && !d->C2 &&
-        !d->R && !d->G && !d->c_rows && d->beta == 0.f &&
-        (d->act == AZ_ACT_NONE || d->act == AZ_ACT_RELU) && d->ldc % 4 == 0 && aligned16(d->C) &&
-        (!d->bias || aligned16(d->bias)) && aligned16(d->ws) && planes && sc &&
-        aligned16(planes)))
-    return 0;
-  GemmArgs a = {};
-  a.M = d->M; a.N = d->N;
-  a.bias = d->bias; a.act = d->act; a.C = write_c ? d->C : nullptr; a.ldc = d->ldc;
-  a.slab = static_cast<float*>(d->ws);
-  a.splits = splits;
-  // one 8-column chunk per thread (N = 3,136: 7 waves; 8.5 -> 8.35 us per M = 512 launch against
-  // two chunks on 4 waves, profiles/r06/reduce_ab)
-  const int T = (d->N / 8 + 63) / 64 * 64;
-  switch (splits) {
-#define AZ_RS(SS) case SS: hipLaunchKernelGGL((splitk_reduce_split_kernel<SS, 1>), dim3(a.M), dim3(T), \
-                                             0, s, a, planes, sc); break;
-    AZ_RS(2) AZ_RS(3) AZ_RS(4) AZ_RS(5) AZ_RS(6) AZ_RS(7) default: AZ_RS(8)
-#undef AZ_RS
-  }
-  const int rc = check_launch("splitk_reduce_split_kernel");
-  return rc == AZ_OK ? 1 : rc;
-}
-
 #ifdef AZ_P3_STAMPS
 }  // namespace az
 extern "C" int az_debug_p3_stamps(void* buf) {   // timing-experiment library only
@@ -4869,8 +3285,8 @@ bool gemm_p2_certain(const az_gemm_desc* d, hipStream_t s) {
         d->K >= 1024 && d->N >= 256 && d->K % 32 == 0 && d->lda % 4 == 0 && d->ldb % 4 == 0 &&
         aligned16(d->A) && aligned16(d->B) && d->ws && d->act != AZ_ACT_DRELU))
     return false;
-  if (tuning_env("AZ_GEMM_X3") || tuning_env("AZ_GEMM_SPLITS") || tuning_env("AZ_GEMM_NOP2") ||
-      tuning_env("AZ_GEMM_PREC") || tuning_env("AZ_GEMM_KSLICE"))
+  if (x3_env_tile() >= 0 || tuning_env("AZ_GEMM_SPLITS") || tuning_env("AZ_GEMM_NOP2") ||
+      tuning_env("AZ_GEMM_PREC"))
     return false;
   const size_t sa_bytes = ((size_t)2 * (d->M + d->N) * sizeof(float) + 255) / 256 * 256;
   if (d->ws_bytes < sa_bytes + 512) return false;

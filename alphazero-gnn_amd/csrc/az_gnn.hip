@@ -10,9 +10,9 @@
 #include <stdlib.h>
 
 #include "az_common.h"
+#include "az_gemm.h"
 
 namespace az {
-int gemm_f32(const az_gemm_desc* d, hipStream_t s);
 bool gnn_layer_fusable(const az_graph* g, int F, int H);
 bool gnn_layer_band_ok(const az_graph* g, int F, int H);
 size_t gnn_layer_band_ws_bytes();

@@ -20,9 +20,9 @@
 #include <stdlib.h>
 
 #include "az_common.h"
+#include "az_gemm.h"
 
 namespace az {
-int gemm_f32(const az_gemm_desc* d, hipStream_t s);
 
 namespace {
 

@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include "az_common.h"
+#include "az_gemm.h"
 #include "az_heads.h"
 #include "az_trunk_split.h"
 #include "az_x3.h"
@@ -185,7 +186,7 @@ __device__ __forceinline__ void trunk_rows_heads(const float* ob, int nb, int b0
 // for output_transform.0 (PreSplitA: two fp16 planes in the p2_chunk layout and scales [2][B], the bits
 // h3_split_rows_kernel would make of feat), so that GEMM needs no split launch of its own.
 // REGW: w2f (non-null) is conv2's weights already split into the fp16 planes of the MFMA B
-// fragments (az_gemm.hip conv2_planes, cached per weight generation, made by w2_planes itself):
+// fragments (az_weights.hip conv2_planes, cached per weight generation, made by w2_planes itself):
 // each lane loads its 9 high and 9 low fragments as 18 coalesced 16-byte loads and its channel's
 // 1 / scale; the LDS staging of w2 (its bank-conflicted scalar stores and reads, a barrier) and
 // the per-wave split are skipped; the registers hold the same values, so the bits are the same.
@@ -948,7 +949,7 @@ __global__ __launch_bounds__(1024) void splitk_heads_rowsw_kernel(
   });
 }
 
-// The split-K reduce of output_transform.0 fused with the composed heads (az_gemm.hip
+// The split-K reduce of output_transform.0 fused with the composed heads (az_weights.hip
 // composed_heads: wp / wv / bp / bv are rows of Wc / bc): a row's slabs are summed in slab order
 // from 0.f, then bias and activation -- splitk_reduce4_kernel's arithmetic, so the hidden rows'
 // bits are splitk_reduce's -- and feed heads_rowsw_body as heads_rowsw_kernel's x rows would;
@@ -1040,7 +1041,6 @@ __global__ __launch_bounds__(512) void c4_trunk_heads_kernel(
 using namespace az;
 
 namespace az {
-const float* conv2_planes(const float* w2, hipStream_t s);   // az_gemm.hip
 
 // The Connect4 trunk launch (az_c4_trunk_fwd); apl / asc non-null: when the chosen NB stages its
 // output in LDS (NB <= 4: B <= 1,024 on 256 CUs) the rows also leave as output_transform.0's
@@ -1199,26 +1199,9 @@ extern "C" int az_conv3x3_relu_fwd(const void* in, int in_int8, int B, int Cin, 
 }
 
 namespace az {
-int gemv1_with_side_heads(const az_gemm_desc* d, const SideHeads* h, hipStream_t s);
-int c4_leaf_fwd(const az_c4_eval* e, const int8_t* boards, int B, float* pi, float* v, float* gpi,
-                float* gv, hipStream_t s);
-int gemm_f32(const az_gemm_desc* d, hipStream_t s);
-int gemm_f32_partial(const az_gemm_desc* d, hipStream_t s, int* splits_out, const PreSplitA* pre,
-                     const HeadsEpi* he = nullptr, bool* heads_done = nullptr);
-int splitk_reduce(const az_gemm_desc* d, int splits, hipStream_t s);
-bool gemm_p2_certain(const az_gemm_desc* d, hipStream_t s);
-int splitk_reduce_split(const az_gemm_desc* d, int splits, unsigned short* planes, float* sc,
-                        hipStream_t s, bool write_c = true);
-bool gemm_p2_weights(const float* w, int n, int k, int ld);
-const float* conv2_planes(const float* w2, hipStream_t s);
-size_t composed_heads_scratch_bytes(int F, int A);
-const float* composed_heads(const float* w2, const float* b2, const float* wp, const float* bp,
-                            const float* wv, const float* bv, int F, int A, float* scratch,
-                            hipStream_t s);
-
 static size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
 
-// The composed-heads path (heads of y = x W^T + b without y: logits = x Wc^T + bc, az_gemm.hip
+// The composed-heads path (heads of y = x W^T + b without y: logits = x Wc^T + bc, az_weights.hip
 // composed_heads) applies to y == NULL, A <= 8 and B above the 64 rows at which the GEMMs switch
 // to the fp16 split form -- a function of the call's shape alone, never of registration or of
 // the GEMM dispatch, so every variant of a call computes the same bits.  Tuning build:

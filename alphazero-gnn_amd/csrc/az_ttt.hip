@@ -5,11 +5,9 @@
 
 #include "az_common.h"
 #include "az_conv_chain.h"
+#include "az_gemm.h"
 
 namespace az {
-int gemm_f32(const az_gemm_desc* d, hipStream_t s);
-int gemv_multi_fwd(const az_gemm_desc* d0, const az_gemm_desc* d1, const az_gemm_desc* d2,
-                   hipStream_t s);
 
 constexpr int TTT_THREADS = 1024;
 

@@ -133,7 +133,7 @@ __device__ __forceinline__ f32x16 mfma6_32x32x16(const bf16x8 (&a)[3], const bf1
 }
 
 // A's rows are scaled into [2^13, 2^14) (fp16 max 65504); W's into [2^9, 2^10): W's scales are
-// cached between weight updates (az_gemm.hip) and stay safe while the weights grow up to 64x.
+// cached between weight updates (az_weights.hip) and stay safe while the weights grow up to 64x.
 constexpr int H3_TA = 14, H3_TW = 10;
 
 // The P2 GEMM's fp16 planes are stored row-interleaved per 32-k step, [rows][K / 32][2][32]:
@@ -166,7 +166,7 @@ struct PreSplitA {
 // B = 512 call than the split-K slabs and the heads pass that re-read them.
 // The stream-K form (gemm_x3_csk) writes one slot per wave instead: t = (64-column block) x
 // max_pieces + piece, and its finalize reads each tile's piece count from the plan.
-// The same linearity lets the evaluators skip the GEMM altogether (az_gemm.hip composed_heads:
+// The same linearity lets the evaluators skip the GEMM altogether (az_weights.hip composed_heads:
 // the heads' rows times W, once per weight generation); this epilogue stays for the tuning
 // build's AZ_NO_COMPOSED_HEADS A/B runs and for workspaces without room for the composed rows.
 constexpr int HEADS_TILE_SLOTS = 9;

@@ -1,4 +1,4 @@
-"""The heads composed with output_transform.2 (csrc/az_gemm.hip composed_heads): for y == NULL,
+"""The heads composed with output_transform.2 (csrc/az_weights.hip composed_heads): for y == NULL,
 A <= 8 and B > 64 the evaluators never run the second GEMM -- the heads are linear in
 y = hidden W2^T + b2 (Connect4GNN.py:106-114 on gnn_utils.py:115's last Linear), so
 logits = hidden Wc^T + bc with Wc = [fc_policy.weight; fc_value.weight] W2 and

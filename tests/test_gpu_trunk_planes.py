@@ -1,4 +1,4 @@
-"""conv2's fp16 fragment planes cached per weight generation (az_gemm.hip conv2_planes) against the
+"""conv2's fp16 fragment planes cached per weight generation (az_weights.hip conv2_planes) against the
 in-kernel split: the Connect4 trunk with its weights in registered storage loads the cached planes
 (the REGW kernels; 4-wave blocks above B = 512), with the same values in plain unregistered tensors
 it stages conv2 through LDS and splits it in every wave.  Both must give the same bits -- the

@@ -55,7 +55,7 @@ def run(M, plan):
     if r.returncode != 0:
         return {"error": r.stderr[-400:]}
     out = json.loads(r.stdout.strip().splitlines()[-1])
-    out["plan_used"] = info[-1] if info else "gemm_x3_sk (no csk)"
+    out["plan_used"] = info[-1] if info else "split-K tiles (no csk)"
     return out
 
 

@@ -1,5 +1,7 @@
-"""GEMM tuning sweep on the GPU box: time az_gemm_f32 for the output_transform shape under
-tile/split overrides (each variant in its own subprocess since the overrides are read once)."""
+"""GEMM tuning sweep on the GPU box: time az_gemm_f32 under the tuning build's overrides (each
+variant in its own subprocess since the overrides are read once):
+    tallk                    gemm_tall (default dispatch) vs the tile kernels on the GNN shapes
+    x3 Ms tiles splits       gemm_x3 tile 1 (256x128) / 2 (128x128) and split-K vs the fp32 tiles"""
 import json
 import os
 os.environ.setdefault("AZ_TUNING_LIB", "1")   # A/B switches live in the tuning build
@@ -45,61 +47,7 @@ def run(env, M=512, N=3136, K=3136):
 
 
 if __name__ == "__main__":
-    mode = sys.argv[1] if len(sys.argv) > 1 else "sweep"
-    if mode == "quick":
-        for (M, N, K) in [(512, 3136, 3136), (4096, 3136, 3136), (64, 3136, 3136)]:
-            for cfg in ("0", "1", "2", "3", "4", "5"):
-                for sk in ("0", "1"):
-                    res = run({"AZ_GEMM_CFG": cfg, "AZ_GEMM_STREAMK": sk}, M, N, K)
-                    print(json.dumps({"M": M, "cfg": cfg, "streamk": sk, **res}), flush=True)
-        sys.exit(0)
-    if mode == "quickcheck":      # one small run per glds config: correctness before the sweep
-        for cfg in sys.argv[2].split(",") if len(sys.argv) > 2 else ("6", "7", "8", "9"):
-            for (M, N, K) in [(100, 200, 96), (100, 200, 100), (512, 3136, 3136)]:
-                res = run({"AZ_GEMM_CFG": cfg}, M, N, K)
-                print(json.dumps({"M": M, "N": N, "K": K, "cfg": cfg, **res}), flush=True)
-                if "error" in res or res.get("rel_err", 1) > 1e-5:
-                    sys.exit(3)
-        sys.exit(0)
-    if mode == "glds":
-        cfgs = sys.argv[2].split(",") if len(sys.argv) > 2 else ("0", "6", "7", "8", "9")
-        splits = sys.argv[3].split(",") if len(sys.argv) > 3 else ("", "2", "3", "4", "5", "6",
-                                                                   "8")
-        for (M, N, K) in [(512, 3136, 3136), (256, 3136, 3136), (4096, 3136, 3136)]:
-            for cfg in cfgs:
-                for sp in splits:
-                    env = {"AZ_GEMM_CFG": cfg}
-                    if sp == "auto":
-                        sp = ""
-                    if sp:
-                        env["AZ_GEMM_SPLITS"] = sp
-                    res = run(env, M, N, K)
-                    print(json.dumps({"M": M, "cfg": cfg, "splits": sp or "auto", **res}),
-                          flush=True)
-        sys.exit(0)
-    if mode == "tall":         # config-5 GNN layer shapes: M = V of 512 grids, K <= 128
-        for (M, N, K) in [(524288, 256, 64), (524288, 64, 64), (524288, 64, 128)]:
-            for cfg in sys.argv[2].split(","):
-                env = {"AZ_GEMM_CFG": cfg} if cfg != "auto" else {}
-                res = run(env, M, N, K)
-                print(json.dumps({"M": M, "N": N, "K": K, "cfg": cfg, **res}), flush=True)
-        sys.exit(0)
-    if mode == "tallabl":      # epilogue-store ablation on the tall shapes (results wrong by design)
-        for (M, N, K) in [(524288, 256, 64), (524288, 64, 64)]:
-            for cfg in sys.argv[2].split(","):
-                for abl in ("0", "4"):
-                    res = run({"AZ_GEMM_CFG": cfg, "AZ_GEMM_ABLATE": abl}, M, N, K)
-                    print(json.dumps({"M": M, "N": N, "K": K, "cfg": cfg, "ablate": abl, **res}),
-                          flush=True)
-        sys.exit(0)
-    if mode == "longk":        # steady state: K 10x longer, fixed splits (per-block overhead amortised)
-        for cfg in sys.argv[2].split(","):
-            for abl in sys.argv[3].split(","):
-                res = run({"AZ_GEMM_CFG": cfg, "AZ_GEMM_ABLATE": abl, "AZ_GEMM_SPLITS": "5"},
-                          512, 3136, 31360)
-                print(json.dumps({"M": 512, "K": 31360, "cfg": cfg, "ablate": abl, **res}),
-                      flush=True)
-        sys.exit(0)
+    mode = sys.argv[1] if len(sys.argv) > 1 else ""
     if mode == "tallk":        # gemm_tall (default dispatch) vs the tile kernels (AZ_GEMM_NOTALL)
         for (M, N, K) in [(524288, 256, 64), (524288, 64, 64), (524288, 64, 128),
                           (524288, 128, 64), (20007, 64, 64)]:
@@ -107,27 +55,6 @@ if __name__ == "__main__":
                         {"AZ_GEMM_ABLATE": "8"}):
                 res = run(env, M, N, K)
                 print(json.dumps({"M": M, "N": N, "K": K, "env": env, **res}), flush=True)
-        sys.exit(0)
-    if mode == "kslice":       # gemm_kslice (M = 512) vs the split-K tile (default dispatch)
-        for env in ({"AZ_GEMM_KSLICE": "1"}, {}):
-            print(json.dumps({"env": env, **run(env)}), flush=True)
-        sys.exit(0)
-    if mode == "mgrid":        # default dispatch vs cfg x split at given M (self-play batch sizes)
-        Ms = [int(x) for x in sys.argv[2].split(",")]
-        cfgs = sys.argv[3].split(",")
-        splits = sys.argv[4].split(",")
-        for M in Ms:
-            print(json.dumps({"M": M, "cfg": "default", **run({}, M=M)}), flush=True)
-            for cfg in cfgs:
-                for sp in splits:
-                    r = run({"AZ_GEMM_CFG": cfg, "AZ_GEMM_SPLITS": sp}, M=M)
-                    print(json.dumps({"M": M, "cfg": cfg, "splits": sp, **r}), flush=True)
-        sys.exit(0)
-    if mode == "bigm":         # large-batch output_transform (also B = 65,536)
-        M = int(sys.argv[3]) if len(sys.argv) > 3 else 65536
-        for cfg in sys.argv[2].split(","):
-            r = run({"AZ_GEMM_CFG": cfg, "AZ_GEMM_SPLITS": "1"}, M=M)
-            print(json.dumps({"M": M, "cfg": cfg, **r}), flush=True)
         sys.exit(0)
     if mode == "x3":           # fp32 on the bf16 matrix cores (gemm_x3) vs the fp32 MFMA tiles
         # argv: Ms  tiles  splits ("auto" = the dispatch's own choice)
@@ -146,21 +73,4 @@ if __name__ == "__main__":
                     print(json.dumps({"M": M, "N": N, "K": K, "x3": t, "splits": sp,
                                       **run(env, M, N, K)}), flush=True)
         sys.exit(0)
-    if mode == "ablate":       # glds2 timing ablations (results wrong by design)
-        cfgs = sys.argv[2].split(",") if len(sys.argv) > 2 else ("15", "16")
-        abls = sys.argv[3].split(",") if len(sys.argv) > 3 else ("0", "1", "2", "3")
-        for (M, N, K) in [(512, 3136, 3136), (4096, 3136, 3136)]:
-            for cfg in cfgs:
-                for abl in abls:
-                    res = run({"AZ_GEMM_CFG": cfg, "AZ_GEMM_ABLATE": abl}, M, N, K)
-                    print(json.dumps({"M": M, "cfg": cfg, "ablate": abl, **res}), flush=True)
-        sys.exit(0)
-    shapes = [(512, 3136, 3136), (4096, 3136, 3136), (64, 3136, 3136), (64, 6272, 3136),
-              (4096, 256, 64)]
-    for (M, N, K) in shapes:
-        for cfg in ("0", "1", "2", "3", "4", "5"):
-            for sk in ("0", "1"):
-                res = run({"AZ_GEMM_CFG": cfg, "AZ_GEMM_STREAMK": sk}, M, N, K)
-                print(json.dumps({"M": M, "N": N, "K": K, "cfg": cfg, "streamk": sk, **res}),
-                      flush=True)
-        print(json.dumps({"M": M, "N": N, "K": K, "cfg": "auto", **run({}, M, N, K)}), flush=True)
+    sys.exit("usage: gemm_sweep.py tallk | x3 Ms tiles(1,2) splits")

@@ -1,5 +1,5 @@
 """GEMV timing for the small-batch evaluation: y = relu(x W^T + b), W 3136 x 3136, M = 1..8 rows,
-events over 200 back-to-back launches; AZ_GEMV_ROWS (tuning build) picks the gemv_rows shape."""
+events over 200 back-to-back launches."""
 import json
 import os
 import sys
@@ -15,7 +15,7 @@ g = torch.Generator().manual_seed(0)
 w = ((torch.rand((N, K), generator=g) * 2 - 1) / K ** 0.5).cuda()
 b = torch.rand((N,), generator=g).cuda()
 x = torch.rand((8, K), generator=g).cuda()
-out = {"rows": os.environ.get("AZ_GEMV_ROWS", "default")}
+out = {}
 for M in range(1, 9):
     xm = x[:M].contiguous()
     y = torch.empty((M, N), device="cuda")

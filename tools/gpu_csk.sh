@@ -1,4 +1,4 @@
-# Cycled stream-K A/B (tools/csk_probe.py, tuning build): plans vs gemm_x3_sk at self-play M
+# Cycled stream-K A/B (tools/csk_probe.py, tuning build): plans vs the split-K tiles (off) at self-play M
 set -u
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp

@@ -1,5 +1,5 @@
 # PMC of the self-play GEMM (ops.linear 3136 x 3136 at M) as the product runs it (gemm_x3_csk) and
-# as round 3 ran it (tuning build, AZ_CSK=off: gemm_x3_sk): FETCH_SIZE, WRITE_SIZE, TCC hit/miss +
+# on the split-K tiles (tuning build, AZ_CSK=off): FETCH_SIZE, WRITE_SIZE, TCC hit/miss +
 # GRBM, SQ busy counters, kernel trace -- each its own rocprofv3 run.
 #   bash tools/gpu_csk_pmc.sh TAG "800 1576 3150"     summary: python tools/csk_pmc_report.py gpurun_out/cskpmc_TAG
 set -u

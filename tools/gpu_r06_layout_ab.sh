@@ -11,7 +11,6 @@ P="python -u tools/p2h_probe.py 512,800,1576,3150 100"
 for i in 1 2; do
   AZ_AB_LIB=libaz_hip_base.so timeout -k 10 180 $P > $O/p2h_base_$i.jsonl 2>&1 || exit 1
   timeout -k 10 180 $P > $O/p2h_new_$i.jsonl 2>&1 || exit 1
-  AZ_TUNING_LIB=1 AZ_P3_RING=2 timeout -k 10 180 $P > $O/p2h_ring2_$i.jsonl 2>&1 || exit 1
 done
 B="python bench.py --full --steps 200 --warmup 20 --no-cpu --no-grid --no-train --no-b1 --no-aggregate --large-batch 0 --sp-check 0"
 for i in 1 2; do

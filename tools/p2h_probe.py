@@ -1,8 +1,8 @@
-"""fp16-form GEMM on pre-split planes (tuning tile 16; with AZ_P3_REUSE=1 the planes are split
-once, so the call is the tile kernel + reduce) vs the product fp16 form splitting in the tile
-(tuning tile 1): HIP-event time per call, error vs float64, a hash of the output bits.  One
-process per tile (the dispatch reads its environment once):
-    AZ_TUNING_LIB=1 AZ_GEMM_X3=16 AZ_P3_REUSE=1 python tools/p2h_probe.py 512,4096 [reps]"""
+"""fp16-form GEMM on pre-split planes (the product dispatch for registered weights) vs splitting
+in the tile (tuning build, AZ_GEMM_NOP2=1, or AZ_GEMM_X3=1 / 2 to force a tile): HIP-event time
+per call, error vs float64, a hash of the output bits.  One process per variant (the dispatch
+reads its environment once):
+    [AZ_TUNING_LIB=1 AZ_GEMM_NOP2=1] python tools/p2h_probe.py 512,4096 [reps]"""
 import hashlib
 import json
 import os

@@ -1,6 +1,5 @@
 """A/B of the 256x128 LDS-DMA tile variants on the output_transform shape (each run in its own
-subprocess): AZ_GEMM_RING = 2 (default 2-buffer), 3 (3-buffer ring), 4 (ring + stagger),
-5 / 6 (the same two with the 32x32x2 MFMA).
+subprocess): AZ_GEMM_RING = 2 (default 2-buffer), 3 (3-buffer ring), 4 (ring + stagger).
     python tools/ring_probe.py [M ...]"""
 import json
 import os
@@ -11,7 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gemm_sweep import run  # noqa: E402
 
 Ms = [int(a) for a in sys.argv[1:]] or [512, 768, 1024, 65536]
-RINGS = os.environ.get("RINGS", "2,3,4,5,6").split(",")
+RINGS = os.environ.get("RINGS", "2,3,4").split(",")
 for M in Ms:
     for rep in range(2):
         for ring in RINGS:
