@@ -1230,7 +1230,11 @@ __global__ __launch_bounds__(512) void gemm_x3_csk(GemmArgs p, CskPlan q) {
     nt0 = (l - r * q.Ct) * q.at;          // in 256-column units
     bma = 128;
   }
-  const int W = am * an * q.KT;           // <= 256 x 98 steps: int arithmetic throughout
+  // int arithmetic throughout: the largest product below and in csk_block_of is b * W with
+  // b * (cycles) <= CUs and am * an * (cycles) <= tiles, so b * W <= CUs * tiles * KT / cycles^2.
+  // One cycle of 256 blocks at K = 4,096 (KT = 128) gives 2^15 * tiles: in range below 65,536
+  // tiles of 256 x 128 (M * N < 2^31); the evaluators' shapes (<= 512 tiles) reach 2^24.
+  const int W = am * an * q.KT;
   int i0 = r * W / b;
   const int i1 = (r + 1) * W / b;
   while (i0 < i1) {
@@ -3471,6 +3475,7 @@ extern "C" int az_gemm_f32(const az_gemm_desc* d, void* stream) {
 extern "C" int az_gemm_form(int M, int N, int K, size_t ws_bytes) {
   if (M <= 8) return 0;
   if (!(M > 64 && K >= 1024 && N >= 256)) return 1;
-  const size_t sa_bytes = ((size_t)2 * M * sizeof(float) + 255) / 256 * 256;
+  // launch_x3's expression: A's scales [2][M] and room for an unregistered W's [2][N]
+  const size_t sa_bytes = ((size_t)2 * (M + N) * sizeof(float) + 255) / 256 * 256;
   return ws_bytes >= sa_bytes + 256 ? 3 : 6;
 }

@@ -1436,7 +1436,8 @@ static int linear_heads_impl(const float* x, int B, int F, const float* w, const
   int S = 1;
   // the tile partials [B][P][9] (P <= ceil(F / 128) * 8) at the start of the slab region
   const size_t tiles_bytes = (size_t)B * ((F + 127) / 128) * 8 * HEADS_TILE_SLOTS * 4;
-  // (the stream-K form's slots: 49 column blocks x its max pieces, <= 8 for these shapes)
+  // (the stream-K form's slots are F / 64 column blocks x its max pieces -- 49 blocks at
+  // F = 3,136, 64 at 4,096; launch_x3 checks that they fit before it takes that form)
   const HeadsEpi he{wp, wv, A, static_cast<float*>(slabs), 0, bp, bv, logp, pi, v};
   bool heads_done = false;
   static const bool no_tiles = tuning_env("AZ_NO_HEADS_TILES") != nullptr;   // A/B experiments

@@ -63,24 +63,24 @@ def _eager(n, B):
     return _EAGER[(n, B)]
 
 
-def _evaluator(n):
-    """(C4nEval for MAX_B boards, its four NaN-filled output tensors), one per n."""
-    if n not in _EVALS:
+def _evaluator(n, max_B=MAX_B):
+    """(C4nEval for max_B boards, its four output tensors), one per (n, max_B)."""
+    if (n, max_B) not in _EVALS:
         from azhip import ops
         nnet, gnn = _nets(n)
         dev = nnet.params.device
-        ev = ops.C4nEval(nnet.params, gnn.params, n, n + 1, MAX_B, dev)
-        outs = [torch.empty((MAX_B, n + 1) if i % 2 == 0 else (MAX_B,), device=dev)
+        ev = ops.C4nEval(nnet.params, gnn.params, n, n + 1, max_B, dev)
+        outs = [torch.empty((max_B, n + 1) if i % 2 == 0 else (max_B,), device=dev)
                 for i in range(4)]
-        _EVALS[n] = (ev, outs)
-    return _EVALS[n]
+        _EVALS[(n, max_B)] = (ev, outs)
+    return _EVALS[(n, max_B)]
 
 
-def _run(n, b, B, kind):
+def _run(n, b, B, kind, max_B=MAX_B):
     """One az_c4n_eval_fwd call of `kind` with every scratch and output NaN before it -> the four
     outputs as numpy (None where the kind has none); rows B.. must stay NaN."""
     from azhip import ops
-    ev, outs = _evaluator(n)
+    ev, outs = _evaluator(n, max_B)
     use = [kind != "gnn", kind != "gnn", kind != "std", kind != "std"]
     for t in (ev.feat, ev.hidden, ev.logp, ev.glogp, *outs):
         t.fill_(float("nan"))
@@ -186,6 +186,30 @@ def test_eval_matches_float64_restatement(n):
               f"margin {TOL / max(max(errs), 1e-300):.1f}x")
         for k, name in enumerate(("pi", "v", "pi_gnn", "v_gnn")):
             assert_close(f"c4n_eval/n{n}/B{B}/{name}", got[k], ref[k], TOL)
+
+
+# Lock-step self-play batch sizes per board side (derived from the GEMM dispatch for 256 CUs and
+# the widths' table in tests/test_gpu_gemm_widths.py): a 256 x 128 split-K size and a stream-K
+# size of F = 64 n^2; the second evaluator per n is sized for the larger one
+LOCKSTEP_B = {4: (257, 2049), 5: (257, 1025), 6: (257, 769), 8: (257, 513)}
+
+
+@pytest.mark.parametrize("n,B", [(n, B) for n in SIDES for B in LOCKSTEP_B[n]])
+def test_eval_at_lockstep_batch_sizes(n, B):
+    """The evaluator at hundreds to thousands of boards (its own C4nEval of max_B = the stream-K
+    size, so the MAX_B = 70 evaluator's workspace and plans above stay as they are): pi, v, gpi
+    and gv within 1e-5 of the float64 restatement and np.array_equal to the eager path; rows
+    B..max_B stay NaN (_run); the empty and the full board are rows 0 and 1."""
+    nnet, gnn = _nets(n)
+    max_B = LOCKSTEP_B[n][1]
+    e = _eager(n, B)
+    ref = _float64_reference(e.b.cpu().numpy(), nnet.params, gnn.params)
+    eager = [x.cpu().numpy() for x in (e.pi, e.v, e.gpi, e.gv)]
+    got = _run(n, e.b, B, "both", max_B)
+    for k, name in enumerate(("pi", "v", "pi_gnn", "v_gnn")):
+        assert_close(f"c4n_eval/n{n}/B{B}/{name}", got[k], ref[k], TOL)
+    for k, name in enumerate(("pi", "v", "pi_gnn", "v_gnn")):
+        assert np.array_equal(got[k], eager[k]), (n, B, name)
 
 
 def _wrapper(n, gnn=True, seed=0):

@@ -80,25 +80,40 @@ def x3_bound(K, lam=8.0):
     return 3 * 2.0 ** -22 + lam * np.sqrt(n) * U32
 
 
+def x3_reference(x, w, b):
+    """(float64 x w^T + b, sum_k |x_k w_k| + |b|): the reference and the magnitude x3_bound is a
+    multiple of, as float64 torch tensors (CPU; shared by the width tests)."""
+    xd, wd, bd = x.double(), w.double(), b.double()
+    return xd @ wd.T + bd, xd.abs() @ wd.abs().T + bd.abs()
+
+
+def x3_ratio(y, ref, mag):
+    """|y - ref| / mag per element (numpy float64): what is held against x3_bound(K)."""
+    return (y.double() - ref).abs().numpy() / (mag.numpy() + 1e-300)
+
+
+def x3_report(rep):
+    """Append `rep` to $AZ_REPORT_DIR/x3_accuracy.jsonl (no-op without the variable)."""
+    d = os.environ.get("AZ_REPORT_DIR")
+    if d:
+        import json
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, "x3_accuracy.jsonl"), "a") as f:
+            f.write(json.dumps(rep) + "\n")
+
+
 def _x3_check(ops, x, w, b, rows=None, report=None):
     """x3 GEMM (M x K) @ (N x K)^T + b against float64 on `rows` (all when None)."""
     y = ops.linear(x.cuda(), w.cuda(), b.cuda(), act=0).cpu().double()
     xs = x if rows is None else x[rows]
     ys = y if rows is None else y[rows]
-    ref = xs.double() @ w.double().T + b.double()
-    bound = (xs.double().abs() @ w.double().abs().T + b.double().abs()).numpy()
-    e = (ys - ref).abs().numpy() / (bound + 1e-300)
+    e = x3_ratio(ys, *x3_reference(xs, w, b))
     lim = x3_bound(x.shape[1])
     rep = {"M": x.shape[0], "N": w.shape[0], "K": x.shape[1], "x3_max": float(e.max()),
            "x3_mean": float(e.mean()), "bound": lim}
     if report:
         rep.update(report)
-        d = os.environ.get("AZ_REPORT_DIR")
-        if d:
-            import json
-            os.makedirs(d, exist_ok=True)
-            with open(os.path.join(d, "x3_accuracy.jsonl"), "a") as f:
-                f.write(json.dumps(rep) + "\n")
+        x3_report(rep)
     assert e.max() <= lim, rep
     return rep
 

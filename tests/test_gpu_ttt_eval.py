@@ -243,6 +243,30 @@ def test_ttt5_new_route_matches_float64_restatement():
         assert_close(f"ttt_eval/ttt5/both8/{name}", both[k], ref[k][:8], TOL)
 
 
+@pytest.mark.parametrize("B", [257, 700])
+def test_ttt5_lockstep_batches_match_float64_restatement(B):
+    """n = 5 at lock-step batch sizes: one az_ttt_eval_fwd call on 257 and 700 boards (fc1 / fc2
+    are 1152 -> 512 and output_transform 1152 -> 1152 GEMMs on the 256 x 128 split-K tiles)
+    against the float64 restatement at 1e-5, all four outputs; every scratch and output buffer
+    NaN before the call, rows B.. untouched."""
+    from azhip import ops
+    W, G = _state_dicts(5)
+    nnet, gnn = _nets(5)
+    dev = nnet.params.device
+    boards = _boards(5, B, 500 + B)
+    ref = _float64_reference(boards, W, G)
+    ev = ops.TttEval(nnet.params, gnn.params, 5, 26, B + 3, dev)
+    outs = [torch.empty((B + 3, 26) if i % 2 == 0 else (B + 3,), device=dev) for i in range(4)]
+    for t in (ev.feat, ev.h1, ev.h2, ev.hidden, ev.y, ev.logp, ev.glogp, *outs):
+        t.fill_(float("nan"))
+    ops.ttt_eval(ev, torch.from_numpy(boards).to(dev), B, *outs)
+    torch.cuda.synchronize()
+    for k, name in enumerate(("pi", "v", "pi_gnn", "v_gnn")):
+        got = outs[k].cpu().numpy()
+        assert np.isnan(got[B:]).all(), (B, name)
+        assert_close(f"ttt_eval/ttt5/B{B}/{name}", got[:B], ref[k], TOL)
+
+
 def test_arena_speculative_batches_equal_batch1_ttt():
     """TicTacToe 3x3 arena, golden GNN weights, 6 games at 25 simulations: speculative leaf
     batches play exactly the games of batch-1 leaves and serve some leaves from their rows."""
