@@ -9,6 +9,9 @@ backward kernels + a fused Adam over the flat parameter buffer).
                dead work is skipped.
 
 Every step takes device tensors: boards int8 [B,n,n], target pi fp32 [B,A], target v fp32 [B].
+Any board side n runs; the gradients of both steps are checked against float64 autograd for
+Connect4 at n = 4..8 (tests/test_gpu_grads_boards.py, tests/test_gpu_train.py) and for
+TicTacToe at n = 3..5 (tests/test_gpu_grads_ragged.py).
 """
 import torch
 

@@ -1,7 +1,8 @@
 """Shared helpers of the backward tests (not a test module).
 
 * check_grad / abs_contributions: the gradient criterion of tests/test_gpu_train.py (its
-  docstring derives it), used unchanged by tests/test_gpu_grads_ragged.py.
+  docstring derives it), used unchanged by tests/test_gpu_grads_ragged.py and
+  tests/test_gpu_grads_boards.py, with the targets, boards and autograd references they share.
 * Plain float64 references of the backward helper kernels, written from the formulas in
   include/az_hip.h alone (no azhip import): tests/test_backward_refs.py checks them on the CPU
   against torch (unfold / autograd), tests/test_gpu_backward_kernels.py compares the HIP kernels
@@ -99,20 +100,93 @@ def cu(a, dtype=None):
     return (t.to(dtype) if dtype is not None else t).cuda()
 
 
-def make_net(kind, W, G=None, dropout=0.0, n=3):
-    """Connect4Net (7x7) or TicTacToeNet (n x n) on the weights W, with a PolicyValueGNN on G."""
+def make_net(kind, W, G=None, dropout=0.0, n=None):
+    """Connect4Net (n x n, A = n + 1, F = 64 n^2; default n = 7) or TicTacToeNet (n x n, default
+    n = 3) on the weights W, with a two-layer PolicyValueGNN(F) on G.  Connect4 training is
+    checked at n = 4..8 (tests/test_gpu_grads_boards.py and, at 7, test_gpu_train.py /
+    test_gpu_grads_ragged.py), TicTacToe at 3..5."""
     from types import SimpleNamespace
     from azhip import nets
     if kind == "c4":
-        game = SimpleNamespace(getBoardSize=lambda: (7, 7), getActionSize=lambda: 8)
+        n = 7 if n is None else n
+        game = SimpleNamespace(getBoardSize=lambda: (n, n), getActionSize=lambda: n + 1)
         net = nets.Connect4Net(game, {"dropout": dropout}, init=W)
-        F = 3136
+        F = 64 * n * n
     else:
+        n = 3 if n is None else n
         game = SimpleNamespace(getBoardSize=lambda: (n, n), getActionSize=lambda: n * n + 1)
         net = nets.TicTacToeNet(game, {}, init=W)
         F = 128 * (n - 2) * (n - 2)
     gnn = nets.PolicyValueGNN(F, 2, init=G) if G is not None else None
     return net, gnn
+
+
+# ------------------------------------------------------------------- whole-network gradients
+def targets(B, A, seed):
+    """Training targets: pi rows from Dirichlet(1), z uniform in (-1, 1), fp32."""
+    rng = np.random.default_rng(seed)
+    return (rng.dirichlet(np.ones(A), B).astype(np.float32),
+            rng.uniform(-1, 1, B).astype(np.float32))
+
+
+def random_boards(n, B, seed):
+    return np.random.default_rng(seed).integers(-1, 2, size=(B, n, n)).astype(np.int8)
+
+
+def ref_grads(fn, W, dtype):
+    """Autograd gradients of the loss fn(P) of oracle.torch_ref on the weights W in `dtype`."""
+    from oracle import torch_ref as R
+    P = R.params(W, dtype)
+    fn(P).backward()
+    return {k: v.grad.numpy() for k, v in P.items() if v.grad is not None}
+
+
+def check_cnn_grads(name, net, W, fn, guard=None):
+    """net.params.grads against float64 / float32 autograd of fn with S from abs_contributions
+    (check_grad's criterion), every tensor of W; `guard(name, g64, S)` sees the float64
+    reference before anything is compared."""
+    import torch
+    from oracle import torch_ref as R
+    got = {k: v.cpu().numpy() for k, v in net.params.grads.items()}
+    g64, g32 = ref_grads(fn, W, torch.float64), ref_grads(fn, W, torch.float32)
+    S = abs_contributions(fn, R.params(W, torch.float64))
+    assert set(g64) == set(W)
+    if guard is not None:
+        guard(name, g64, S)
+    for k in g64:
+        check_grad(f"{name}/{k}", got[k], g64[k], g32[k], S[k])
+
+
+MIN_LIVE = 1.0 / 8
+
+
+def guard_reference(name, g64, S, all_zero=()):
+    """A reference that is mostly zeros checks nothing, so before a comparison:
+
+    * every float64 reference tensor has a non-zero maximum;
+    * of a tensor other than a bias, counting the elements that any term reaches at all
+      (S > 0: an element whose every term |dy| |x| is exactly zero -- a dead ReLU unit, a dropped
+      or ReLU-zero feature -- is zero by the network's structure, in the reference and in any
+      correct kernel), at most half are exact zeros, and at least MIN_LIVE of the tensor is
+      reached.  MIN_LIVE = 1/8: the sparsest gradients here are outer products of ONE row pair
+      (a batch of one, the star's single destination), a ReLU'd row (about half live) times a
+      ReLU'd row kept with probability 0.7 (about 0.35 live), 0.175 of the tensor.
+
+    `all_zero` names the tensors (by a part of the key) that the case makes identically zero -- the
+    attention MLP on a one-edge star, whose single normalised weight is 1 whatever the logit:
+    they must be exactly zero instead."""
+    for k, g in g64.items():
+        g, live = np.asarray(g), np.asarray(S[k]) > 0
+        if any(s in k for s in all_zero):
+            assert not g.any(), (name, k, "expected identically zero")
+            continue
+        assert np.abs(g).max() > 0, (name, k, "all-zero reference")
+        if k.endswith("bias"):
+            continue
+        zeros_live = int(((g == 0) & live).sum())
+        assert not (g[~live] != 0).any(), (name, k)
+        assert 2 * zeros_live <= int(live.sum()), (name, k, zeros_live, int(live.sum()))
+        assert live.mean() >= MIN_LIVE, (name, k, float(live.mean()))
 
 
 # ------------------------------------------------------------------------------ references
@@ -210,6 +284,11 @@ TN_SHAPES = [(32, 9, 1), (32, 9, 1617), (128, 576, 1), (128, 576, 33), (64, 288,
              (256, 64, 1027), (64, 64, 4099)]
 NN_SHAPES = [(1, 576, 128), (9, 288, 64), (33, 128, 64), (297, 576, 128)]
 TN_EXTRA_ROWS = 37     # rows of the larger B that the b_rows case gathers K of
+# The training path's GEMMs at the Connect4 board widths F = 64 n^2, n = 4, 5, 6, 8: F x F
+# weight gradients over K rows (the first two split K, with a K tail in the last split), and
+# node_update_bwd's B x 2F input gradient with K = F (M = 1: the star's single destination)
+TN_BOARD_SHAPES = [(1024, 1024, 257), (1600, 1600, 300), (2304, 2304, 33), (4096, 4096, 1)]
+NN_BOARD_SHAPES = [(33, 2048, 1024), (9, 3200, 1600), (1, 4608, 2304), (3, 8192, 4096)]
 
 
 def tn_inputs(M, N, K):
@@ -231,17 +310,22 @@ def nn_inputs(M, N, K):
 
 
 HEADS_A = (1, 8, 9, 16, 17, 26, 32)
-HEADS_K = (4, 252, 260, 3136)
+HEADS_K = (4, 252, 260, 3136, 1600)     # 1600 = 64 * 5^2: six 256-column blocks and a quarter
 HEADS_FORMS = ("c4", "ttt", "wonly", "dhonly")
 
 
 def heads_bwd_cases():
     """(A, K, B, form): every A, every K and every call form with B = 3 and with B = 65, and
-    two single-row cases."""
+    two single-row cases.  The first four K cycle over the seven A; K = 1600 cycles once over
+    the four forms with every other A (B = 3: A = 1, 9, 17, 32; B = 65: A = 8, 16, 26, 1), so
+    each form and each of the three kernel instances meets the partial seventh block."""
     cases = []
     for bi, B in enumerate((3, 65)):
         for i, A in enumerate(HEADS_A):
             cases.append((A, HEADS_K[(i + bi) % 4], B, HEADS_FORMS[(i + 2 * bi) % 4]))
+    for bi, B in enumerate((3, 65)):
+        for j, form in enumerate(HEADS_FORMS):
+            cases.append((HEADS_A[(2 * j + bi) % len(HEADS_A)], HEADS_K[4], B, form))
     return cases + [(17, 260, 1, "c4"), (1, 4, 1, "ttt")]
 
 
@@ -261,8 +345,12 @@ def colsum_inputs(R, C):
     return ints(rng, (R, C)), ints(rng, (C,))
 
 
-COL2IM_HW = ((3, 3), (4, 4), (5, 4), (7, 7))
-IM2COL_HW = ((3, 3), (4, 5), (7, 7))
+COL2IM_HW = ((3, 3), (4, 4), (5, 4), (7, 7), (5, 5), (6, 6), (8, 8))
+IM2COL_HW = ((3, 3), (4, 5), (7, 7), (5, 5), (6, 6), (8, 8))
+# (B, C, HW) of az_nchw_drelu_to_pm: the TicTacToe heads and conv3, Connect4 7x7, and Connect4's
+# conv2 output on 4x4 / 5x5 / 6x6 / 8x8 boards
+NCHW_PM_SHAPES = ((1, 512, 1), (3, 128, 4), (5, 64, 49), (3, 64, 16), (2, 64, 25), (2, 64, 36),
+                  (1, 64, 64))
 
 
 def col2im_inputs(B, C, H, W, pad, ldc):

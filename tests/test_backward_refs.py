@@ -20,7 +20,7 @@ def _unfold_cols(x, pad):
 
 @pytest.mark.parametrize("C", [1, 3])
 @pytest.mark.parametrize("pad", [0, 1])
-@pytest.mark.parametrize("H,W", [(3, 3), (4, 5), (5, 4), (7, 7)])
+@pytest.mark.parametrize("H,W", [(3, 3), (4, 5), (5, 4), (7, 7), (5, 5), (6, 6), (8, 8)])
 def test_im2col_ref_is_unfold(C, pad, H, W):
     rng = np.random.default_rng(C * 100 + pad * 10 + H + W)
     x = rng.standard_normal((3, C, H, W))
@@ -35,7 +35,7 @@ def test_im2col_ref_is_unfold(C, pad, H, W):
 
 @pytest.mark.parametrize("C", [2, 32])
 @pytest.mark.parametrize("pad", [0, 1])
-@pytest.mark.parametrize("H,W", [(3, 3), (4, 4), (5, 4), (7, 7)])
+@pytest.mark.parametrize("H,W", [(3, 3), (4, 4), (5, 4), (7, 7), (5, 5), (6, 6), (8, 8)])
 def test_col2im_ref_is_autograd_of_unfold(C, pad, H, W):
     rng = np.random.default_rng(C * 100 + pad * 10 + H + W)
     B = 2
@@ -51,7 +51,7 @@ def test_col2im_ref_is_autograd_of_unfold(C, pad, H, W):
     np.testing.assert_allclose(gc.col2im3x3_drelu_ref(dcols, a, pad), want, rtol=0, atol=1e-13)
 
 
-@pytest.mark.parametrize("B,C,HW", [(1, 512, 1), (3, 128, 4), (5, 64, 49)])
+@pytest.mark.parametrize("B,C,HW", gc.NCHW_PM_SHAPES)
 def test_nchw_drelu_to_pm_ref_is_autograd(B, C, HW):
     """s = dropout(relu(pre)) in NCHW from a position-major pre [B*HW][C]: d loss / d pre for
     loss = sum(s * dy) is the kernel's dz."""
@@ -124,7 +124,7 @@ def _is_small_int(*arrays):
     return all(np.array_equal(a, np.round(a)) and np.abs(a).max() <= 3 for a in arrays)
 
 
-@pytest.mark.parametrize("M,N,K", gc.TN_SHAPES)
+@pytest.mark.parametrize("M,N,K", gc.TN_SHAPES + gc.TN_BOARD_SHAPES)
 def test_tn_integer_data_is_exact_in_fp32(M, N, K):
     a, b, rows, c0 = gc.tn_inputs(M, N, K)
     assert _is_small_int(a, b, c0) and len(set(rows.tolist())) == K
@@ -133,7 +133,7 @@ def test_tn_integer_data_is_exact_in_fp32(M, N, K):
         assert (a64.T @ np.abs(bb) + np.abs(c0)).max() < EXACT
 
 
-@pytest.mark.parametrize("M,N,K", gc.NN_SHAPES)
+@pytest.mark.parametrize("M,N,K", gc.NN_SHAPES + gc.NN_BOARD_SHAPES)
 def test_nn_integer_data_is_exact_in_fp32(M, N, K):
     a, b, g, c0 = gc.nn_inputs(M, N, K)
     assert _is_small_int(a, b, g, c0) and (g == 0).any() and (g < 0).any()

@@ -7,8 +7,11 @@ product and partial sum is then exact in any order (test_backward_refs.py assert
 sum of |products| of each case is below 2^24), the comparison is equality, and one dropped,
 doubled or misplaced element fails.  Outputs start as NaN, so an element that is never written
 fails too; padding that a kernel must not read is NaN as well.  az_heads_loss_bwd (expf) is
-compared against float64 with a bound derived per element."""
+compared against float64 with a bound derived per element.  The shape tables of
+tests/gradcheck.py carry the Connect4 4x4 .. 8x8 boards' shapes (C = 64, HW = 16 / 25 / 36 / 64,
+K = 1600 in az_heads_bwd), and the transposed GEMM forms run at their widths F = 64 n^2 too."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -91,7 +94,7 @@ def test_col2im3x3_drelu(L, pad, H, W, C):
 
 
 # ------------------------------------------------------------------------------ nchw_drelu_to_pm
-@pytest.mark.parametrize("B,C,HW", [(1, 512, 1), (3, 128, 4), (5, 64, 49)])
+@pytest.mark.parametrize("B,C,HW", gc.NCHW_PM_SHAPES)
 @pytest.mark.parametrize("masked", [False, True])
 def test_nchw_drelu_to_pm(L, B, C, HW, masked):
     rng = np.random.default_rng(B * C + HW)
@@ -208,8 +211,8 @@ def _heads_bwd_case(ops, A, K, B, form, ldh=None):
 @pytest.mark.parametrize("A,K,B,form", gc.heads_bwd_cases())
 def test_heads_bwd(ops, A, K, B, form):
     """c4: hv is hp and one fused dh; ttt: separate hp / hv, dh and dhv; wonly: weight grads
-    only; dhonly: dh and dhv only.  A <= 8 / <= 16 / <= 32 are three kernel instances; K = 252
-    and 260 end inside a 256-column block."""
+    only; dhonly: dh and dhv only.  A <= 8 / <= 16 / <= 32 are three kernel instances; K = 252,
+    260 and 1600 (a 5x5 Connect4 board) end inside a 256-column block."""
     _heads_bwd_case(ops, A, K, B, form)
 
 
@@ -344,11 +347,109 @@ def test_gemm_nn_ragged(ops, M, N, K, form):
         same(C, ref)
 
 
+# ------------------------------------------------- the transposed forms at the board widths
+EXACT = 2 ** 24
+WS_BYTES = 256 << 20           # ops.workspace's default, what _run(split=True) hands the library
+
+
+def tn_planned_splits(M, N, K, ws_bytes=WS_BYTES):
+    """plan()'s rule (csrc/az_gemm.hip) for the 64 x 64 x 32 register tile every transposed form
+    takes, restated: with fewer than 1024 tiles K is cut into min(ceil(1024 / tiles), 8,
+    K // 128) parts (at least four 32-k steps each) whose M x N slabs fit the workspace; each
+    part is a whole number of k steps, so the count is ceil(K / kc)."""
+    tiles = -(-M // 64) * -(-N // 64)
+    S = min(-(-1024 // tiles), 8, K // 128) if tiles < 1024 else 1
+    while S > 1 and S * M * N * 4 > ws_bytes:
+        S -= 1
+    if S <= 1:
+        return 1, K
+    kc = -(-(-(-K // S)) // 32) * 32
+    return -(-K // kc), kc
+
+
+@functools.lru_cache(maxsize=None)
+def _tn_board_case(M, N, K):
+    """Operands of one board-width TN shape and the float64 products of the plain and the
+    gathered form, computed once; the exactness condition is asserted on them."""
+    a0, b0, rows0, c0 = _tn_operands(M, N, K)
+    a64 = a0.astype(np.float64).T
+    plain = a64 @ b0[:K, :N].astype(np.float64)
+    gathered = a64 @ b0[rows0][:, :N].astype(np.float64)
+    for bb in (b0[:K, :N], b0[rows0][:, :N]):
+        assert (np.abs(a64) @ np.abs(bb).astype(np.float64) + np.abs(c0)).max() < EXACT
+    return a0, b0, rows0, c0, plain, gathered
+
+
+@pytest.mark.parametrize("M,N,K", gc.TN_BOARD_SHAPES)
+@pytest.mark.parametrize("form", ["beta0", "beta1", "column_half", "b_rows"])
+def test_gemm_tn_at_board_widths(ops, M, N, K, form):
+    """C = a^T b, the F x F weight gradients of az_mlp2_bwd / node_update_bwd at F = 64 n^2 for
+    the 4x4 .. 8x8 Connect4 boards, with a split workspace: plain with beta 0 and 1, into a column
+    half (ldc = 2N, C offset by N columns, the other half keeps its sentinel), and with b_rows
+    gathering K unsorted rows of a larger B.  Integer operands in {-3..3}: every sum is below 2^24
+    (asserted on the CPU product), so the fp32 result equals the float64 product.
+
+    The library does not report the split count of a launch, so the test restates plan()'s rule
+    (tn_planned_splits) and asserts the class it gives: (1024, 1024, 257) and (1600, 1600, 300)
+    are cut in two with a K tail in the second part, (2304, 2304, 33) and (4096, 4096, 1) are
+    not cut; the count is printed."""
+    S, kc = tn_planned_splits(M, N, K)
+    print(f"gemm_tn_board/M{M}_N{N}_K{K}: planned splits {S}, {kc} k per split")
+    assert (S, kc) == {257: (2, 160), 300: (2, 160), 33: (1, 33), 1: (1, 1)}[K]
+    assert S == 1 or 0 < K - (S - 1) * kc < kc            # the last part is a partial one
+    a0, b0, rows0, c0, plain, gathered = _tn_board_case(M, N, K)
+    a, b = cu(a0), cu(b0)
+    if form == "column_half":
+        full = torch.full((M, 2 * N), 7777.0, device="cuda")
+        C = full[:, N:]
+        _run(ops, _desc(ops, M, N, K, a, M, 0, b, b.stride(0), C, 2 * N), True)
+        same(C, plain)
+        assert bool((full[:, :N] == 7777.0).all())
+        return
+    beta = 1.0 if form == "beta1" else 0.0
+    C = cu(c0) if beta else nans(M, N)
+    rows = cu(rows0) if form == "b_rows" else None
+    _run(ops, _desc(ops, M, N, K, a, M, 0, b, b.stride(0), C, N, beta=beta, b_rows=rows), True)
+    same(C, (gathered if form == "b_rows" else plain) + beta * c0)
+
+
+@functools.lru_cache(maxsize=None)
+def _nn_board_case(M, N, K):
+    a0, b0, g0, c0 = gc.nn_inputs(M, N, K)
+    assert (g0 == 0).any() and (g0 < 0).any()
+    assert (np.abs(a0).astype(np.float64) @ np.abs(b0) + np.abs(c0)).max() < EXACT
+    return a0, b0, g0, c0, a0.astype(np.float64) @ b0.astype(np.float64)
+
+
+@pytest.mark.parametrize("M,N,K", gc.NN_BOARD_SHAPES)
+@pytest.mark.parametrize("form", ["plain", "drelu", "beta1"])
+def test_gemm_nn_at_board_widths(ops, M, N, K, form):
+    """C = a b with an N-major b at N = 2F, K = F: node_update_bwd's dc = du1pre Wu1 + dgpre Wg
+    on the four boards (M = 1 is the star's single destination), plain, through the DRELU gate
+    (zeros and negatives in it) and accumulating, each with and without a split workspace.
+    Integer operands, sums below 2^24 (asserted), equality with the float64 product."""
+    a0, b0, g0, c0, ref = _nn_board_case(M, N, K)
+    if form == "drelu":
+        ref = ref * (g0 > 0)
+    elif form == "beta1":
+        ref = ref + c0
+    a, b = cu(a0), cu(b0)
+    G = cu(g0) if form == "drelu" else None
+    for split in (True, False):
+        C = cu(c0) if form == "beta1" else nans(M, N)
+        d = _desc(ops, M, N, K, a, K, 1, b, N, C, N, beta=1.0 if form == "beta1" else 0.0,
+                  act=ops.ACT_DRELU if form == "drelu" else 0, G=G)
+        _run(ops, d, split)
+        same(C, ref)
+
+
 @pytest.mark.parametrize("form,M,N,K", [("tn", 64, 64, 4099), ("tn", 32, 9, 1617),
-                                        ("nn", 297, 576, 128)])
+                                        ("nn", 297, 576, 128), ("tn", 1600, 1600, 300),
+                                        ("nn", 9, 3200, 1600)])
 def test_gemm_transposed_forms_real_valued(ops, form, M, N, K):
     """Uniform +-1 data against float64 at 1e-6 of sum |a b|: a reduced-precision path would pass
-    the integer cases above."""
+    the integer cases above and below.  The last two are a 5x5 Connect4 board's F x F weight
+    gradient (two K splits) and its node_update_bwd input gradient."""
     rng = np.random.default_rng(M + N + K)
     b0 = rng.uniform(-1, 1, (K, gc.up4(N))).astype(np.float32)
     C = nans(M, N)

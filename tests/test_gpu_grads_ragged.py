@@ -18,6 +18,8 @@ torch = pytest.importorskip("torch")
 
 import gradcheck as gc  # noqa: E402
 from gradcheck import abs_contributions, check_grad, cu, make_net  # noqa: E402
+from gradcheck import check_cnn_grads as _check_cnn, ref_grads as _ref  # noqa: E402
+from gradcheck import random_boards, targets  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -26,33 +28,6 @@ pytestmark = pytest.mark.gpu
 def lib():
     from azhip import _lib
     return _lib.lib()
-
-
-def targets(B, A, seed):
-    rng = np.random.default_rng(seed)
-    return (rng.dirichlet(np.ones(A), B).astype(np.float32),
-            rng.uniform(-1, 1, B).astype(np.float32))
-
-
-def random_boards(n, B, seed):
-    return np.random.default_rng(seed).integers(-1, 2, size=(B, n, n)).astype(np.int8)
-
-
-def _ref(fn, W, dtype):
-    from oracle import torch_ref as R
-    P = R.params(W, dtype)
-    fn(P).backward()
-    return {k: v.grad.numpy() for k, v in P.items() if v.grad is not None}
-
-
-def _check_cnn(name, net, W, fn):
-    from oracle import torch_ref as R
-    got = {k: v.cpu().numpy() for k, v in net.params.grads.items()}
-    g64, g32 = _ref(fn, W, torch.float64), _ref(fn, W, torch.float32)
-    S = abs_contributions(fn, R.params(W, torch.float64))
-    assert set(g64) == set(W)
-    for k in g64:
-        check_grad(f"{name}/{k}", got[k], g64[k], g32[k], S[k])
 
 
 def _ttt_weights(n):
