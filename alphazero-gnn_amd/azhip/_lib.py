@@ -80,6 +80,11 @@ class C4nEval(ctypes.Structure):
     _fields_ = C4Eval._fields_[:-2] + [("n", c_int), ("F", c_int)]
 
 
+class C4rEval(ctypes.Structure):
+    """az_c4r_eval (include/az_hip.h): az_c4n_eval's fields with nx, ny in place of n."""
+    _fields_ = C4Eval._fields_[:-2] + [("nx", c_int), ("ny", c_int), ("F", c_int)]
+
+
 class TttEval(ctypes.Structure):
     """az_ttt_eval (include/az_hip.h)."""
     _fields_ = ([(f"{l}_{k}", c_void_p) for l in ("conv1", "conv2", "conv3", "fc1", "fc2",
@@ -130,6 +135,15 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "az_c4n_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "az_c4n_eval_fwd": (c_int, [ctypes.POINTER(C4nEval), c_void_p, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p]),
+    "az_c4r_trunk_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "az_c4r_trunk_heads_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "az_c4r_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "az_c4r_eval_fwd": (c_int, [ctypes.POINTER(C4rEval), c_void_p, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
     "az_ttt_trunk_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -70,25 +70,43 @@ class Connect4Net(_Net):
         self.action_size = game.getActionSize()
         self.args = args
         self.dropout = _args_get(args, "dropout", 0.3)
-        self.n = self.board_x
+        self.n = self.board_x            # columns (the side of a square board)
         self.feature_dim = 64 * self.board_x * self.board_y
-        spec = connect4_net_spec(self.n, self.action_size)
+        spec = connect4_net_spec((self.board_x, self.board_y), self.action_size)
         self.params = FlatParams(spec, device or default_device(),
                                  init if init is not None else torch_default_init(spec))
         self.training = True
 
+    @property
+    def route(self):
+        """Which trunk the board shape (board_x columns, board_y rows) takes: "c4" the 7x7 MFMA
+        trunk, "c4n" the fused launch for the square sides in ops.C4N_SIDES, "c4r" the fused
+        launch for the rectangular shapes in ops.C4R_SHAPES, "eager" the two conv launches.  The
+        test is on both extents: a 7-column board of another height is not the 7x7 board."""
+        x, y = self.board_x, self.board_y
+        if x == y:
+            return "c4" if x == 7 else "c4n" if x in ops.C4N_SIDES else "eager"
+        return "c4r" if (x, y) in ops.C4R_SHAPES else "eager"
+
     def features(self, b):
-        """b: int8 [B,n,n] on HBM -> [B, 64*n*n] (Connect4Net.py:42-49)."""
+        """b: int8 [B,cols,rows] on HBM -> [B, 64*cols*rows] (Connect4Net.py:42-49): the conv
+        input is [B,1,cols,rows] (H = cols, W = rows), feature c*cols*rows + x*rows + y."""
         W = self.params
         W.sync()
-        if self.n == 7:
+        if tuple(b.shape[1:]) != (self.board_x, self.board_y):
+            raise ValueError(f"Connect4Net for a {self.board_x}x{self.board_y} board got boards "
+                             f"of shape {tuple(b.shape)}")
+        route = self.route
+        if route == "c4":
             return ops.c4_trunk(b, W)
-        if self.n in ops.C4N_SIDES:      # one launch, bit-identical to features_eager
+        if route == "c4n":               # one launch, bit-identical to features_eager
             return ops.c4n_trunk(b, W)
+        if route == "c4r":
+            return ops.c4r_trunk(b, W)
         return self.features_eager(b)
 
     def features_eager(self, b):
-        """The two conv3x3_relu launches (any n)."""
+        """The two conv3x3_relu launches (any board shape)."""
         W = self.params
         W.sync()
         s = ops.conv3x3_relu(b, W["conv1.weight"], W["conv1.bias"], 1)
@@ -97,16 +115,19 @@ class Connect4Net(_Net):
 
     def features_heads(self, b, pi=None, v=None):
         """features(b) and heads of them -> (feat, logp, pi, v), bit-identical to the two calls:
-        one launch for small B on the 7x7 board (ops.c4_trunk_heads) and at every B on 4x4, 5x5,
-        6x6 and 8x8 (ops.c4n_trunk_heads)."""
-        if self.n in ops.C4N_SIDES:
-            self.params.sync()
-            return ops.c4n_trunk_heads(b, self.params, pi=pi, v=v)
-        if self.n != 7:
+        one launch for small B on the 7x7 board (ops.c4_trunk_heads), at every B on 4x4, 5x5,
+        6x6 and 8x8 (ops.c4n_trunk_heads) and on 7x6, 6x5, 5x4 and 8x7 (ops.c4r_trunk_heads)."""
+        route = self.route
+        if route == "eager":
             f = self.features(b)
             return (f,) + self.heads(f, pi=pi, v=v)
+        if tuple(b.shape[1:]) != (self.board_x, self.board_y):
+            raise ValueError(f"Connect4Net for a {self.board_x}x{self.board_y} board got boards "
+                             f"of shape {tuple(b.shape)}")
         self.params.sync()
-        return ops.c4_trunk_heads(b, self.params, pi=pi, v=v)
+        fn = {"c4": ops.c4_trunk_heads, "c4n": ops.c4n_trunk_heads,
+              "c4r": ops.c4r_trunk_heads}[route]
+        return fn(b, self.params, pi=pi, v=v)
 
     def heads(self, feat, want_pi=True, pi=None, v=None):
         """Connect4GNN.py:48-57 (pi / v: optional output buffers, e.g. HostBuffer views)."""

@@ -376,6 +376,83 @@ def c4n_eval(ev, boards_i8, B, pi=None, v=None, gpi=None, gv=None, stream=None):
                                           _p(gpi), _p(gv), s), "az_c4n_eval_fwd")
 
 
+# (cols, rows) of az_c4r_*: the standard Connect4 board and its nearest relatives
+C4R_SHAPES = ((7, 6), (6, 5), (5, 4), (8, 7))
+
+
+def c4r_trunk(boards_i8, W, out=None):
+    """Connect4Net conv1 + conv2 (+ ReLU) in one launch (az_c4r_trunk_fwd): int8 boards
+    [B,cols,rows], (cols, rows) in C4R_SHAPES -> features [B, 64 cols rows], bit-identical to two
+    conv3x3_relu calls."""
+    _need(boards_i8, torch.int8, "boards")
+    B, nx, ny = boards_i8.shape
+    if out is None:
+        out = torch.empty((B, 64 * nx * ny), device=_dev(boards_i8), dtype=torch.float32)
+    L = _lib.lib()
+    _lib.check(L.az_c4r_trunk_fwd(_p(boards_i8), B, nx, ny, _p(W["conv1.weight"]),
+                                  _p(W["conv1.bias"]), _p(W["conv2.weight"]), _p(W["conv2.bias"]),
+                                  _p(out), _stream()), "az_c4r_trunk_fwd")
+    return out
+
+
+def c4r_trunk_heads(boards_i8, W, feat=None, logp=None, pi=None, v=None, want_pi=True):
+    """Trunk + policy/value heads (Connect4Net.py:42-60) on a cols x rows board in C4R_SHAPES ->
+    (feat, logp, pi, v) in ONE launch at every B, bit-identical to c4r_trunk then heads."""
+    _need(boards_i8, torch.int8, "boards")
+    B, nx, ny = boards_i8.shape
+    dev = _dev(boards_i8)
+    A = W["fc_policy.weight"].shape[0]
+    feat = torch.empty((B, 64 * nx * ny), device=dev) if feat is None else feat
+    logp = torch.empty((B, A), device=dev) if logp is None else logp
+    pi = (torch.empty((B, A), device=dev) if pi is None else pi) if want_pi else None
+    v = torch.empty((B,), device=dev) if v is None else v
+    _lib.check(_lib.lib().az_c4r_trunk_heads_fwd(
+        _p(boards_i8), B, nx, ny, _p(W["conv1.weight"]), _p(W["conv1.bias"]),
+        _p(W["conv2.weight"]), _p(W["conv2.bias"]), _p(W["fc_policy.weight"]),
+        _p(W["fc_policy.bias"]), A, _p(W["fc_value.weight"]), _p(W["fc_value.bias"]), _p(feat),
+        _p(logp), _p(pi), _p(v), _stream()), "az_c4r_trunk_heads_fwd")
+    return feat, logp, pi, v
+
+
+class C4rEval:
+    """az_c4r_eval descriptor with its device scratch for up to max_B boards of a cols x rows
+    Connect4Net (`shape` = (cols, rows) in C4R_SHAPES): W the net's parameter tensors, G the
+    PolicyValueGNN's (None: no GNN tail, no workspace).  The tensors are read through the pointers
+    taken here, so they must be updated in place."""
+
+    def __init__(self, W, G, shape, A, max_B, device):
+        nx, ny = (int(s) for s in shape)
+        F = 64 * nx * ny
+        self.shape, self.A, self.F, self.max_B = (nx, ny), A, F, max_B
+        e = lambda *s: torch.empty(s, device=device, dtype=torch.float32)  # noqa: E731
+        nb = int(_lib.lib().az_c4r_eval_ws_bytes(max_B, nx, ny, A))
+        if nb == 0:
+            raise ValueError(f"az_c4r_eval: unsupported shape cols={nx} rows={ny} A={A} "
+                             f"max_B={max_B}")
+        self.feat = e(max_B, F)
+        self.hidden = e(max_B, F) if G is not None else None
+        self.logp, self.glogp = e(max_B, A), e(max_B, A)
+        self.ws = torch.empty((nb,), dtype=torch.uint8, device=device) if G is not None else None
+        P = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        ot = [P(G[f"output_transform.{i}.{k}"]) if G is not None else None
+              for i in (0, 2) for k in ("weight", "bias")]
+        self.desc = _lib.C4rEval(
+            *[P(W[f"{l}.{k}"]) for l in ("conv1", "conv2", "fc_policy", "fc_value")
+              for k in ("weight", "bias")],
+            A, *ot, max_B, P(self.feat), P(self.hidden), None, P(self.logp), P(self.glogp),
+            P(self.ws), nb if G is not None else 0, nx, ny, F)
+        self._keep = (W, G)
+
+
+def c4r_eval(ev, boards_i8, B, pi=None, v=None, gpi=None, gv=None, stream=None):
+    """az_c4r_eval_fwd on `ev` (a C4rEval): the first B boards -> pi / v (standard heads) and
+    gpi / gv (GNN tail), each written when given; device tensors or HostBuffer views.  Queued on
+    `stream` (default: the current stream); nothing is synchronised."""
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(_lib.lib().az_c4r_eval_fwd(ctypes.byref(ev.desc), _p(boards_i8), B, _p(pi), _p(v),
+                                          _p(gpi), _p(gv), s), "az_c4r_eval_fwd")
+
+
 def heads(hp, wp, bp, wv, bv, hv=None, want_pi=True, logp=None, pi=None, v=None):
     """logp = log_softmax(hp wp^T + bp); v = tanh(hv wv^T + bv) (hv defaults to hp)."""
     hv = hp if hv is None else hv

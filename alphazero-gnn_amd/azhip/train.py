@@ -8,10 +8,11 @@ backward kernels + a fused Adam over the flat parameter buffer).
                nnet_optimizer.zero_grad() (Connect4GNN.py:154) discards them unused, so that
                dead work is skipped.
 
-Every step takes device tensors: boards int8 [B,n,n], target pi fp32 [B,A], target v fp32 [B].
-Any board side n runs; the gradients of both steps are checked against float64 autograd for
-Connect4 at n = 4..8 (tests/test_gpu_grads_boards.py, tests/test_gpu_train.py) and for
-TicTacToe at n = 3..5 (tests/test_gpu_grads_ragged.py).
+Every step takes device tensors: boards int8 [B,cols,rows], target pi fp32 [B,A], target v fp32
+[B].  Any board shape runs; the gradients of both steps are checked against float64 autograd for
+Connect4 at n = 4..8 (tests/test_gpu_grads_boards.py, tests/test_gpu_train.py) and on 7x6, 5x4
+and 4x6 (tests/test_gpu_grads_rect.py), and for TicTacToe at n = 3..5
+(tests/test_gpu_grads_ragged.py).
 """
 import torch
 
@@ -41,7 +42,7 @@ class C4Forward:
         W = _views(net)
         self.boards = boards
         self.B = boards.shape[0]
-        self.n = net.n
+        self.HW = boards.shape[1] * boards.shape[2]              # cols * rows
         self.feat = net.features(boards)                         # a2 = relu(conv2), NCHW flat
         self.p = float(drop_p)
         self.mask = mask
@@ -53,9 +54,8 @@ class C4Forward:
         self.W = W
 
     def trunk_backward(self, ds, G):
-        """ds: d loss / d (dropped features) [B, 64*n*n] -> conv grads into G."""
-        W, B, n = self.W, self.B, self.n
-        HW = n * n
+        """ds: d loss / d (dropped features) [B, 64*cols*rows] -> conv grads into G."""
+        W, B, HW = self.W, self.B, self.HW
         dz2 = ops.nchw_drelu_to_pm(ds, self.feat, B, 64, HW, mask=self.mask, scale=self.scale)
         a1 = ops.conv3x3_relu(self.boards, W["conv1.weight"], W["conv1.bias"], 1)
         cols2 = ops.im2col3x3(a1, 1)                                          # [B*HW, 288]

@@ -23,9 +23,11 @@ import numpy as np
 
 
 def connect4_net_spec(n=7, action_size=None):
-    """connect4/Connect4Net.py:18-25 (board n x n, A = n + 1, Connect4Game.py:139-141)."""
-    a = n + 1 if action_size is None else action_size
-    f = 64 * n * n
+    """connect4/Connect4Net.py:18-25.  `n` is the side of a square board or (cols, rows):
+    A = cols + 1 (Connect4Game.py:139-141), F = 64 * cols * rows, fc_policy [A][F]."""
+    cols, rows = (n, n) if np.isscalar(n) else (int(n[0]), int(n[1]))
+    a = cols + 1 if action_size is None else action_size
+    f = 64 * cols * rows
     return [
         ("conv1.weight", (32, 1, 3, 3)), ("conv1.bias", (32,)),
         ("conv2.weight", (64, 32, 3, 3)), ("conv2.bias", (64,)),

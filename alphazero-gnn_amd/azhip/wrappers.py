@@ -206,6 +206,28 @@ class _C4nDirectBatch(_DirectBatch):
         self.cap = cap
 
 
+class _C4rDirectBatch(_DirectBatch):
+    """_DirectBatch for the Connect4Net on the rectangular boards of ops.C4R_SHAPES (7x6, 6x5, 5x4,
+    8x7): ONE az_c4r_eval_fwd call per batch, same host ring, same ownership tokens.  Without a
+    GNN (the CNN-only wrapper) only `both=False` batches exist and the descriptor carries no
+    output_transform (and no workspace)."""
+
+    def __init__(self, w, stream=None):
+        super().__init__(w, stream)
+        self.fn = _lib.lib().az_c4r_eval_fwd
+        self.fn_name = "az_c4r_eval_fwd"
+
+    def _grow(self, n):
+        w = self.w
+        cap = max(1024, 1 << (int(n) - 1).bit_length())
+        torch.cuda.synchronize(w.device)          # in-flight batches may use the old scratch
+        self.ev = ops.C4rEval(w.nnet.params, w.gnn.params if w.has_gnn else None,
+                              (w.board_x, w.board_y), w.action_size, cap, w.device)
+        self.desc = self.ev.desc
+        self.ring = []        # entries still held by unread predictions keep their buffers
+        self.cap = cap
+
+
 class _PinnedRing:
     """Pinned host staging buffers reused round-robin (`depth` predictions in flight)."""
 
@@ -437,6 +459,11 @@ class _TttBatch1Direct(_Batch1Direct):
     eval_class = ops.TttEval
     fn_name = "az_ttt_eval_fwd"
 
+    @staticmethod
+    def _board_arg(w):
+        """What eval_class takes for the board: the side."""
+        return w.nnet.n
+
     def __init__(self, w, kind, cap=1):
         dev = w.device
         A = w.action_size
@@ -447,8 +474,8 @@ class _TttBatch1Direct(_Batch1Direct):
         self.host = ops.HostBuffer(256 * cap + 4 * width * cap)
         self.h_in = self.host.view(0, torch.int8, (cap, w.board_x, w.board_y))
         self.h_out = self.host.view(256 * cap, torch.float32, (cap * width,))
-        self.ev = self.eval_class(w.nnet.params, w.gnn.params if gnn else None, w.nnet.n, A, cap,
-                                  dev)
+        self.ev = self.eval_class(w.nnet.params, w.gnn.params if gnn else None,
+                                  self._board_arg(w), A, cap, dev)
         self.desc = self.ev.desc
         self.err_np = None
         o = self.h_out.numpy()
@@ -480,8 +507,31 @@ class _C4nBatch1Direct(_TttBatch1Direct):
     fn_name = "az_c4n_eval_fwd"
 
 
+class _C4rBatch1Direct(_TttBatch1Direct):
+    """_Batch1Direct for the Connect4Net on the rectangular boards of ops.C4R_SHAPES (7x6, 6x5,
+    5x4, 8x7): up to `cap` boards as ONE az_c4r_eval_fwd call (1 launch for std, 4 for gnn / both;
+    no in-kernel hand-over, so no timeout path).  Same host layout, run() and run_rows() as the
+    7x7 evaluator."""
+
+    eval_class = ops.C4rEval
+    fn_name = "az_c4r_eval_fwd"
+
+    @staticmethod
+    def _board_arg(w):
+        return (w.board_x, w.board_y)
+
+
+def _c4_shape(w):
+    """(columns, rows) of a Connect4Net wrapper's board, None for another network.  Both extents
+    count: a 7-column board that is not 7 rows high is NOT the 7x7 board of az_c4_*."""
+    net = w.nnet
+    if not isinstance(net, nets.Connect4Net):
+        return None
+    return (getattr(net, "board_x", net.n), getattr(net, "board_y", net.n))
+
+
 def _is_c4(w):
-    return isinstance(w.nnet, nets.Connect4Net) and w.nnet.n == 7
+    return _c4_shape(w) == (7, 7)
 
 
 def _is_ttt(w):
@@ -489,15 +539,22 @@ def _is_ttt(w):
 
 
 def _is_c4n(w):
-    return isinstance(w.nnet, nets.Connect4Net) and w.nnet.n in ops.C4N_SIDES
+    s = _c4_shape(w)
+    return s is not None and s[0] == s[1] and s[0] in ops.C4N_SIDES
+
+
+def _is_c4r(w):
+    """The rectangular Connect4 boards with a fused trunk and az_c4r_eval_fwd."""
+    return _c4_shape(w) in ops.C4R_SHAPES
 
 
 def _direct_ok(w):
     """az_c4_eval_fwd covers the 7x7 Connect4Net (+ PolicyValueGNN output_transform),
-    az_c4n_eval_fwd the Connect4Net on 4x4, 5x5, 6x6 and 8x8 boards, az_ttt_eval_fwd the
-    TicTacToeNet on 3x3 .. 5x5 boards."""
+    az_c4n_eval_fwd the Connect4Net on 4x4, 5x5, 6x6 and 8x8 boards, az_c4r_eval_fwd the one on
+    7x6, 6x5, 5x4 and 8x7 boards, az_ttt_eval_fwd the TicTacToeNet on 3x3 .. 5x5 boards.  Every
+    other shape (9x9, 4x6, ...) takes the hipGraph / pinned-ring routes."""
     return (os.environ.get("AZ_B1_MODE", "direct") == "direct"
-            and (_is_c4(w) or _is_c4n(w) or _is_ttt(w))
+            and (_is_c4(w) or _is_c4n(w) or _is_c4r(w) or _is_ttt(w))
             and os.environ.get("AZ_NO_ZEROCOPY", "0") in ("", "0"))
 
 
@@ -554,7 +611,8 @@ class NetWrapper:
                 self.gnn.eval()
             if _direct_ok(self):
                 cls = (_TttBatch1Direct if _is_ttt(self) else
-                       _C4nBatch1Direct if _is_c4n(self) else _Batch1Direct)
+                       _C4nBatch1Direct if _is_c4n(self) else
+                       _C4rBatch1Direct if _is_c4r(self) else _Batch1Direct)
                 g[kind] = cls(self, kind, cap=8 if kind == "both" else 1)
             else:
                 g[kind] = _Batch1Graph(self, kind)
@@ -585,7 +643,7 @@ class NetWrapper:
         return out[:-1], out[-1]
 
     def predict_batch(self, boards):
-        """Row-wise predict for [B,n,n] boards -> (pi float32[B,A], v float32[B])."""
+        """Row-wise predict for [B,cols,rows] boards -> (pi float32[B,A], v float32[B])."""
         self.nnet.eval()
         if len(boards) == 1 and (g := self._graph1("std")) is not None:
             out = g.run(boards[0])
@@ -599,14 +657,16 @@ class NetWrapper:
         each lane a stream, so one lane's batch can overlap the other's on the GPU); the caller
         orders the stream after any parameter update (play_episodes_engine does)."""
         self._sync_params()
-        if (self.has_gnn or _is_ttt(self) or _is_c4n(self)) and _direct_ok(self) \
+        if (self.has_gnn or _is_ttt(self) or _is_c4n(self) or _is_c4r(self)) \
+                and _direct_ok(self) \
                 and len(boards) > 0:
             directs = self.__dict__.setdefault("_directs", {})
             key = None if stream is None else stream.cuda_stream
             d = directs.get(key)
             if d is None:
                 cls = (_TttDirectBatch if _is_ttt(self) else
-                       _C4nDirectBatch if _is_c4n(self) else _DirectBatch)
+                       _C4nDirectBatch if _is_c4n(self) else
+                       _C4rDirectBatch if _is_c4r(self) else _DirectBatch)
                 d = directs[key] = cls(self, stream)
             self.nnet.eval()
             if self.has_gnn:
@@ -849,9 +909,10 @@ class GNNWrapperMixin:
     def batch_invariant_rows(self):
         """Largest batch whose predict_both rows are bit-identical to batch-1 calls: the 7x7
         Connect4 evaluator (az_c4_eval_fwd), the one for 4x4, 5x5, 6x6 and 8x8 boards
-        (az_c4n_eval_fwd) and the TicTacToe one (az_ttt_eval_fwd, n = 3..5) compute every row of
-        a batch of <= 8 with the batch-1 arithmetic (tests/test_gpu_selfplay.py,
-        tests/test_gpu_c4n_eval.py, tests/test_gpu_ttt_eval.py); 0 = no such guarantee."""
+        (az_c4n_eval_fwd), the one for 7x6, 6x5, 5x4 and 8x7 boards (az_c4r_eval_fwd) and the
+        TicTacToe one (az_ttt_eval_fwd, n = 3..5) compute every row of a batch of <= 8 with the
+        batch-1 arithmetic (tests/test_gpu_selfplay.py, tests/test_gpu_c4n_eval.py,
+        tests/test_gpu_c4r_eval.py, tests/test_gpu_ttt_eval.py); 0 = no such guarantee."""
         return 8 if _direct_ok(self) else 0
 
     def predict(self, board):

@@ -40,13 +40,13 @@ __global__ __launch_bounds__(C4N_THREADS) void c4n_trunk_heads_kernel(
   __syncthreads();
   for (int idx = tid; idx < 32 * HW; idx += C4N_THREADS) {
     const int co = idx / HW, pos = idx % HW;
-    const float s = conv_chain<1, N, 1, false>(w1 + co * 9, bd, pos / N, pos % N) + b1[co];
+    const float s = conv_chain<1, N, N, 1, false>(w1 + co * 9, bd, pos / N, pos % N) + b1[co];
     p1[pos * 36 + co] = s > 0.f ? s : 0.f;
   }
   __syncthreads();
   for (int idx = tid; idx < F; idx += C4N_THREADS) {
     const int co = idx / HW, pos = idx % HW;
-    const float s = conv_chain<32, N, 1, true>(w2 + co * 32 * 9, p1, pos / N, pos % N) + b2[co];
+    const float s = conv_chain<32, N, N, 1, true>(w2 + co * 32 * 9, p1, pos / N, pos % N) + b2[co];
     tile[idx] = s > 0.f ? s : 0.f;
   }
   __syncthreads();

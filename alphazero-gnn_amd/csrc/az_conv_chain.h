@@ -1,5 +1,5 @@
 // The 3x3 conv fmaf chain on an LDS-resident input, shared by the one-workgroup-per-board trunks
-// (az_ttt.hip, az_c4n.hip).
+// (az_ttt.hip, az_c4n.hip, az_c4r.hip).
 #pragma once
 
 #include "az_common.h"
@@ -9,11 +9,12 @@ namespace az {
 // One output of a 3x3 conv whose input sits in LDS: the fmaf chain of conv3x3_relu_kernel,
 // (ci, kh, kw) order with out-of-range taps skipped (a select, no branch).  w is the output
 // channel's [CIN][3][3] weight row.
-// CIN == 1: `in` is the N x N plane.  Otherwise `in` is position-major, [N*N][CIN + 4] (the pad
+// The input is H x W (row index yo < H, column index xo < W; a square board has H == W).
+// CIN == 1: `in` is the H x W plane.  Otherwise `in` is position-major, [H*W][CIN + 4] (the pad
 // keeps positions on different banks and rows 16-byte aligned): one ds_read_b128 brings a tap's
 // four consecutive input channels, so a step of four channels is 9 LDS reads for 36 fmaf.
 // VEC: a 16-byte aligned weight row, its 36 weights per step arrive as nine float4 loads.
-template <int CIN, int N, int PAD, bool VEC>
+template <int CIN, int H, int W, int PAD, bool VEC>
 __device__ __forceinline__ float conv_chain(const float* __restrict__ w, const float* in, int yo,
                                             int xo) {
   constexpr int LD = CIN == 1 ? 1 : CIN + 4;
@@ -24,9 +25,9 @@ __device__ __forceinline__ float conv_chain(const float* __restrict__ w, const f
 #pragma unroll
     for (int kw = 0; kw < 3; ++kw) {
       const int yi = yo + kh - PAD, xi = xo + kw - PAD;
-      const bool in_range = PAD == 0 || (yi >= 0 && yi < N && xi >= 0 && xi < N);
+      const bool in_range = PAD == 0 || (yi >= 0 && yi < H && xi >= 0 && xi < W);
       ok[kh * 3 + kw] = in_range;
-      off[kh * 3 + kw] = in_range ? (yi * N + xi) * LD : 0;
+      off[kh * 3 + kw] = in_range ? (yi * W + xi) * LD : 0;
     }
   float s = 0.f;
   if constexpr (CIN == 1) {

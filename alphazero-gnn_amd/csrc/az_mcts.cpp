@@ -85,10 +85,10 @@ double pairwise(const double* a, long n) {
 }
 
 // ----------------------------------------------------------------------------- rules
-constexpr int kMaxA = 65;   // actions: n*n + 1 with n*n <= 64 cells
+constexpr int kMaxA = 65;   // actions: n*n + 1 (TicTacToe) or nx + 1 (Connect4), <= 64 cells
 
 struct Key {
-  uint64_t p, q;   // bit i = cell i (i = x*n + y) holds +1 / -1
+  uint64_t p, q;   // bit i = cell i (i = x*ny + y) holds +1 / -1
   bool operator==(const Key& o) const { return p == o.p && q == o.q; }
 };
 
@@ -101,29 +101,37 @@ inline uint64_t mix64(uint64_t z) {
 inline uint64_t khash(const Key& k) { return mix64(k.p ^ mix64(k.q)); }
 
 struct Rules {
-  int game = 0, n = 0, A = 0, cells = 0;
+  // nx columns, ny rows (Connect4: board[x][y], cell x*ny + y; TicTacToe is square, n = nx = ny)
+  int game = 0, n = 0, nx = 0, ny = 0, A = 0, cells = 0;
   std::vector<uint64_t> lines;   // winning line masks
-  uint64_t top = 0;              // Connect4: cells (x, n-1)
+  uint64_t top = 0;              // Connect4: cells (x, ny-1)
   uint64_t all = 0;
 
-  bool init(int g, int nn) {
-    if (nn < 1 || nn * nn > 64 || (g != AZM_GAME_CONNECT4 && g != AZM_GAME_TICTACTOE))
+  bool init(int g, int nn) { return init(g, nn, nn); }
+
+  // Connect4 on nx columns x ny rows; a rectangular board (nx != ny) needs 4 in a row and both
+  // extents >= 4 (Connect4Game(board_size, rows)); the square one keeps min(4, n).
+  bool init(int g, int cx, int cy) {
+    if (cx < 1 || cy < 1 || cx * cy > 64 || (g != AZM_GAME_CONNECT4 && g != AZM_GAME_TICTACTOE))
       return false;
+    if (cx != cy && (g != AZM_GAME_CONNECT4 || cx < 4 || cy < 4)) return false;
     game = g;
-    n = nn;
-    cells = n * n;
+    nx = cx;
+    ny = cy;
+    n = nx;
+    cells = nx * ny;
     all = cells == 64 ? ~0ull : ((1ull << cells) - 1);
-    auto bit = [&](int x, int y) { return 1ull << (x * n + y); };
+    auto bit = [&](int x, int y) { return 1ull << (x * ny + y); };
     if (g == AZM_GAME_CONNECT4) {
-      A = n + 1;
-      int w = n < 4 ? n : 4;                     // min(4, n) in a row (Connect4Game.py:67-99)
-      for (int x = 0; x < n; ++x) top |= bit(x, n - 1);
+      A = nx + 1;
+      int w = nx == ny && n < 4 ? n : 4;         // min(4, n) in a row (Connect4Game.py:67-99)
+      for (int x = 0; x < nx; ++x) top |= bit(x, ny - 1);
       const int dirs[4][2] = {{1, 0}, {0, 1}, {1, 1}, {1, -1}};
       for (auto& d : dirs)
-        for (int x = 0; x < n; ++x)
-          for (int y = 0; y < n; ++y) {
+        for (int x = 0; x < nx; ++x)
+          for (int y = 0; y < ny; ++y) {
             int ex = x + d[0] * (w - 1), ey = y + d[1] * (w - 1);
-            if (ex < 0 || ex >= n || ey < 0 || ey >= n) continue;
+            if (ex < 0 || ex >= nx || ey < 0 || ey >= ny) continue;
             uint64_t m = 0;
             for (int i = 0; i < w; ++i) m |= bit(x + d[0] * i, y + d[1] * i);
             lines.push_back(m);
@@ -214,8 +222,8 @@ struct Rules {
     uint64_t occ = k.p | k.q;
     bool any = false;
     if (game == AZM_GAME_CONNECT4) {
-      for (int x = 0; x < n; ++x) {
-        v[x] = !((occ >> (x * n + n - 1)) & 1);
+      for (int x = 0; x < nx; ++x) {
+        v[x] = !((occ >> (x * ny + ny - 1)) & 1);
         any |= v[x];
       }
     } else {
@@ -236,10 +244,10 @@ struct Rules {
     }
     uint64_t occ = k.p | k.q, b;
     if (game == AZM_GAME_CONNECT4) {
-      uint64_t col = ((occ >> (a * n)) & ((1ull << n) - 1));
-      uint64_t free_ = ~col & ((1ull << n) - 1);
+      uint64_t col = ((occ >> (a * ny)) & ((1ull << ny) - 1));
+      uint64_t free_ = ~col & ((1ull << ny) - 1);
       if (!free_) return false;                  // "Column is full!" (Connect4Game.py:149)
-      b = 1ull << (a * n + __builtin_ctzll(free_));
+      b = 1ull << (a * ny + __builtin_ctzll(free_));
     } else {
       b = 1ull << a;
       if (occ & b) return false;
@@ -1008,13 +1016,13 @@ extern "C" {
 
 const char* az_mcts_last_error(void) { return g_err.c_str(); }
 
-az_mcts* az_mcts_create(int game, int n, int slots, double cpuct, int use_gnn) {
+az_mcts* az_mcts_create_rect(int game, int nx, int ny, int slots, double cpuct, int use_gnn) {
   if (slots < 1) {
     fail(AZM_EINVAL, "az_mcts_create: slots must be >= 1");
     return nullptr;
   }
   az_mcts* m = new az_mcts();
-  if (!m->R.init(game, n)) {
+  if (!m->R.init(game, nx, ny)) {
     delete m;
     fail(AZM_EINVAL, "az_mcts_create: unsupported game / board size (n*n must be <= 64)");
     return nullptr;
@@ -1025,6 +1033,10 @@ az_mcts* az_mcts_create(int game, int n, int slots, double cpuct, int use_gnn) {
   for (auto& t : m->trees) t.clear();
   m->leafbuf.resize((size_t)slots * m->R.cells);
   return m;
+}
+
+az_mcts* az_mcts_create(int game, int n, int slots, double cpuct, int use_gnn) {
+  return az_mcts_create_rect(game, n, n, slots, cpuct, use_gnn);
 }
 
 void az_mcts_destroy(az_mcts* m) { delete m; }
@@ -1579,34 +1591,49 @@ int az_mcts_tree_stats(const az_mcts* m, int slot, int64_t* out) {
   return AZM_OK;
 }
 
-int az_game_ended(int game, int n, const int8_t* board, int* tag, double* value) {
+int az_game_ended_rect(int game, int nx, int ny, const int8_t* board, int* tag, double* value) {
   Rules R;
   Key k;
-  if (!R.init(game, n) || !R.from_board(board, &k)) return fail(AZM_EINVAL, "az_game_ended");
+  if (!R.init(game, nx, ny) || !R.from_board(board, &k))
+    return fail(AZM_EINVAL, "az_game_ended");
   Val v = R.ended(k);
   *tag = v.tag == T_INT ? AZM_TAG_INT : AZM_TAG_FLOAT;
   *value = v.x;
   return AZM_OK;
 }
 
-int az_game_valids(int game, int n, const int8_t* board, int8_t* valids) {
+int az_game_ended(int game, int n, const int8_t* board, int* tag, double* value) {
+  return az_game_ended_rect(game, n, n, board, tag, value);
+}
+
+int az_game_valids_rect(int game, int nx, int ny, const int8_t* board, int8_t* valids) {
   Rules R;
   Key k;
-  if (!R.init(game, n) || !R.from_board(board, &k)) return fail(AZM_EINVAL, "az_game_valids");
+  if (!R.init(game, nx, ny) || !R.from_board(board, &k))
+    return fail(AZM_EINVAL, "az_game_valids");
   std::vector<uint8_t> v(R.A);
   R.valids(k, v.data());
   for (int a = 0; a < R.A; ++a) valids[a] = (int8_t)v[a];
   return AZM_OK;
 }
 
-int az_game_next_canonical(int game, int n, const int8_t* board, int action, int8_t* out) {
+int az_game_valids(int game, int n, const int8_t* board, int8_t* valids) {
+  return az_game_valids_rect(game, n, n, board, valids);
+}
+
+int az_game_next_canonical_rect(int game, int nx, int ny, const int8_t* board, int action,
+                                int8_t* out) {
   Rules R;
   Key k, nk;
-  if (!R.init(game, n) || !R.from_board(board, &k) || action < 0 || action >= R.A)
+  if (!R.init(game, nx, ny) || !R.from_board(board, &k) || action < 0 || action >= R.A)
     return fail(AZM_EINVAL, "az_game_next_canonical: bad args");
   if (!R.next(k, action, &nk)) return fail(AZM_EINVAL, "az_game_next_canonical: illegal move");
   R.to_board(nk, out);
   return AZM_OK;
+}
+
+int az_game_next_canonical(int game, int n, const int8_t* board, int action, int8_t* out) {
+  return az_game_next_canonical_rect(game, n, n, board, action, out);
 }
 
 int az_game_children(int game, int n, const int8_t* board, int cap, int8_t* out) {

@@ -33,19 +33,19 @@ __global__ __launch_bounds__(TTT_THREADS) void ttt_trunk_kernel(
   __syncthreads();
   for (int idx = tid; idx < 32 * HW; idx += TTT_THREADS) {
     const int co = idx / HW, pos = idx % HW;
-    const float s = conv_chain<1, N, 1, false>(w1 + co * 9, bd, pos / N, pos % N) + b1[co];
+    const float s = conv_chain<1, N, N, 1, false>(w1 + co * 9, bd, pos / N, pos % N) + b1[co];
     p1[pos * 36 + co] = s > 0.f ? s : 0.f;
   }
   __syncthreads();
   for (int idx = tid; idx < 64 * HW; idx += TTT_THREADS) {
     const int co = idx / HW, pos = idx % HW;
-    const float s = conv_chain<32, N, 1, VEC>(w2 + co * 32 * 9, p1, pos / N, pos % N) + b2[co];
+    const float s = conv_chain<32, N, N, 1, VEC>(w2 + co * 32 * 9, p1, pos / N, pos % N) + b2[co];
     p2[pos * 68 + co] = s > 0.f ? s : 0.f;
   }
   __syncthreads();
   for (int idx = tid; idx < 128 * HW3; idx += TTT_THREADS) {
     const int co = idx / HW3, pos = idx % HW3;
-    const float s = conv_chain<64, N, 0, VEC>(w3 + co * 64 * 9, p2, pos / M, pos % M) + b3[co];
+    const float s = conv_chain<64, N, N, 0, VEC>(w3 + co * 64 * 9, p2, pos / M, pos % M) + b3[co];
     feat[b * (128 * HW3) + idx] = s > 0.f ? s : 0.f;
   }
 }

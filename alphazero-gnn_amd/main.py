@@ -1,7 +1,8 @@
 """Entry point with the reference's CLI and config.yaml surface (reference main.py:1-58,140-293).
 
     python main.py --game connect4 [--use_gnn] [--gnn_layers 2] [--config connect4/config.yaml]
-                   [--board_size N] [--numIters N] [--numMCTSSims N] [--load_model] [--pit_gnn]
+                   [--board_size N] [--board_rows N] [--numIters N] [--numMCTSSims N]
+                   [--load_model] [--pit_gnn]
 
 YAML sections are flattened into one namespace; --use_gnn / --gnn_layers always override the
 YAML (main.py:217-218), the three numeric overrides only when given.  Checkpoints go to
@@ -83,7 +84,9 @@ def create_game_instance(GameClass, args):
                          is_slippery=args.get("is_slippery", False),
                          render_mode=args.get("render_mode", None))
     if args.game == "connect4":
-        return GameClass(board_size=args.board_size)
+        # board_rows (config key or --board_rows; absent: square): 7 columns x 6 rows is
+        # --board_size 7 --board_rows 6
+        return GameClass(board_size=args.board_size, rows=args.get("board_rows", None))
     return GameClass(**{k: v for k, v in args.items()
                         if k in GameClass.__init__.__code__.co_varnames})
 
@@ -126,6 +129,8 @@ def parse(argv=None):
     p.add_argument("--gnn_layers", type=int, default=2)
     p.add_argument("--pit_gnn", action="store_true")
     p.add_argument("--board_size", type=int)
+    p.add_argument("--board_rows", type=int,
+                   help="Connect4 only: rows of a rectangular board (default: board_size)")
     p.add_argument("--numIters", type=int)
     p.add_argument("--numMCTSSims", type=int)
     p.add_argument("--parallel_games", type=int, default=None)
@@ -148,7 +153,8 @@ def build_args(a):
         log.error(f"Error loading configuration: {e}")
         sys.exit(1)
     args = config_to_args(config)
-    for k in ("board_size", "numIters", "numMCTSSims", "parallel_games", "train_parallel"):
+    for k in ("board_size", "board_rows", "numIters", "numMCTSSims", "parallel_games",
+              "train_parallel"):
         if getattr(a, k) is not None:
             args[k] = getattr(a, k)
     args.use_gnn = a.use_gnn

@@ -38,6 +38,8 @@ _SIGS = {
     "az_mcts_last_error": (ctypes.c_char_p, []),
     "az_mcts_create": (_P, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                             ctypes.c_int]),
+    "az_mcts_create_rect": (_P, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_double, ctypes.c_int]),
     "az_mcts_destroy": (None, [_P]),
     "az_mcts_action_size": (ctypes.c_int, [_P]),
     "az_mcts_reset": (ctypes.c_int, [_P, ctypes.c_int]),
@@ -62,6 +64,10 @@ _SIGS = {
     "az_game_ended": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     "az_game_valids": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, _P]),
     "az_game_next_canonical": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
+    "az_game_ended_rect": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "az_game_valids_rect": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "az_game_next_canonical_rect": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P,
+                                                   ctypes.c_int, _P]),
     "az_game_children": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
     "az_np_pairwise_sum": (ctypes.c_double, [_P, ctypes.c_int]),
     "az_mcts_episode_begin": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
@@ -104,14 +110,31 @@ def _check(rc, what):
     return rc
 
 
-def game_kind(game):
-    """(engine game id, n) for the two registered games; ValueError for anything else."""
+def game_shape(game):
+    """(engine game id, (cols, rows)) for the two registered games; ValueError for anything else
+    and for a board of more than 64 cells (the engine keeps a board in two 64-bit words)."""
     name = type(game).__name__
     if name == "Connect4Game":
-        return GAME_CONNECT4, int(game.board_size)
-    if name == "TicTacToeGame":
-        return GAME_TICTACTOE, int(game.n)
-    raise ValueError(f"native MCTS supports Connect4Game / TicTacToeGame, not {name}")
+        kind, shape = GAME_CONNECT4, (int(game.board_size),
+                                      int(getattr(game, "rows", game.board_size)))
+        square_w = min(4, shape[0])
+        if getattr(game, "win_length", square_w) != (square_w if shape[0] == shape[1] else 4):
+            raise ValueError(f"native MCTS: Connect4 {shape[0]}x{shape[1]} with "
+                             f"{game.win_length} in a row is not an engine rule set")
+    elif name == "TicTacToeGame":
+        kind, shape = GAME_TICTACTOE, (int(game.n), int(game.n))
+    else:
+        raise ValueError(f"native MCTS supports Connect4Game / TicTacToeGame, not {name}")
+    if shape[0] * shape[1] > 64:
+        raise ValueError(f"native MCTS: a {shape[0]}x{shape[1]} board has more than 64 cells")
+    return kind, shape
+
+
+def game_kind(game):
+    """(engine game id, columns) for the two registered games (game_shape carries the rows);
+    ValueError for anything else and for more than 64 cells."""
+    kind, shape = game_shape(game)
+    return kind, shape[0]
 
 
 def typed_q(tag, x):
@@ -127,22 +150,24 @@ class Engine:
     """One libaz_mcts engine: `slots` concurrent game trees of one game kind."""
 
     def __init__(self, game, slots, cpuct, use_gnn):
-        self.kind, self.n = game_kind(game)
-        self.cells = self.n * self.n
+        self.kind, self.shape = game_shape(game)      # (cols, rows); n = cols
+        self.n = self.shape[0]
+        self.cells = self.shape[0] * self.shape[1]
         self.slots = slots
         self.use_gnn = bool(use_gnn)
-        h = lib().az_mcts_create(self.kind, self.n, slots, float(cpuct), int(self.use_gnn))
+        h = lib().az_mcts_create_rect(self.kind, self.shape[0], self.shape[1], slots,
+                                      float(cpuct), int(self.use_gnn))
         if not h:
             raise RuntimeError("az_mcts_create: " + lib().az_mcts_last_error().decode())
         self.h = ctypes.c_void_p(h)
         self.A = lib().az_mcts_action_size(self.h)
-        self.leaf_boards = np.zeros((slots, self.n, self.n), np.int8)
+        self.leaf_boards = np.zeros((slots,) + self.shape, np.int8)
         self.leaf_slots = np.zeros(slots, np.int32)
         self._rem = np.zeros(slots, np.int32)
         self._nsa = np.zeros(self.A, np.int32)
         self._q = np.zeros(self.A, np.float64)
         self._tag = np.zeros(self.A, np.int8)
-        self._b = np.zeros((self.n, self.n), np.int8)
+        self._b = np.zeros(self.shape, np.int8)
         self._pb, self._ps, self._pr = (_ptr(self.leaf_boards), _ptr(self.leaf_slots),
                                         _ptr(self._rem))
         self._pn, self._pq, self._pt, self._pbb = (_ptr(self._nsa), _ptr(self._q),
@@ -154,7 +179,7 @@ class Engine:
         self._stage = [np.zeros((self._scap, self.A), np.float32), np.zeros(self._scap, np.float32),
                        np.zeros((self._scap, self.A), np.float32), np.zeros(self._scap, np.float32)]
         self._sptr = [_ptr(a) for a in self._stage]
-        self._sboards = np.zeros((self._scap, self.n, self.n), np.int8)
+        self._sboards = np.zeros((self._scap,) + self.shape, np.int8)
         self._psb = _ptr(self._sboards)
 
     def __del__(self):
@@ -329,8 +354,8 @@ class Engine:
         _check(lib().az_mcts_episodes_moves(self.h, _ptr(sl), n, _ptr(moves)),
                "az_mcts_episodes_moves")
         tot = int(moves.sum())
-        A, c = self.A, self.n
-        width = {"C": (c, c), "A": (A,), 1: ()}
+        A = self.A
+        width = {"C": self.shape, "A": (A,), 1: ()}
         big = {k: np.empty((tot,) + width[w], dt) for k, dt, w in self._REC}
         tg = {k: np.empty((tot,) + width[w], dt) for k, dt, w in self._TGT} if self.use_gnn else {}
         rtag = np.zeros(n, np.intc)
@@ -355,8 +380,8 @@ class Engine:
     def episode_record(self, slot):
         """Per-move records of a finished episode (see include/az_mcts.h)."""
         n = _check(lib().az_mcts_episode_moves(self.h, slot), "az_mcts_episode_moves")
-        A, c = self.A, self.n
-        r = {"boards": np.zeros((n, c, c), np.int8), "cur": np.zeros(n, np.int8),
+        A = self.A
+        r = {"boards": np.zeros((n,) + self.shape, np.int8), "cur": np.zeros(n, np.int8),
              "temp": np.zeros(n, np.int8), "action": np.zeros(n, np.int32),
              "pi": np.zeros((n, A), np.float64), "init_nsa": np.zeros((n, A), np.int32),
              "init_has": np.zeros((n, A), np.int8), "std_v": np.zeros(n, np.float32),
@@ -593,7 +618,7 @@ class ArenaPlayer:
         self.spec = rows if rows >= 2 else 0
         self.calls = 0
         if self.spec:
-            self._batch = np.zeros((self.spec, self.eng.n, self.eng.n), np.int8)
+            self._batch = np.zeros((self.spec,) + self.eng.shape, np.int8)
             self._pbatch = _ptr(self._batch)
 
     @property

@@ -242,6 +242,63 @@ size_t az_c4n_eval_ws_bytes(int max_B, int n, int A);
 int az_c4n_eval_fwd(const az_c4n_eval* e, const int8_t* boards, int B, float* pi, float* v,
                     float* gpi, float* gv, void* stream);
 
+/* Connect4Net trunk on a rectangular board of nx columns and ny rows, (nx, ny) in {(7, 6), (6, 5),
+ * (5, 4), (8, 7)} -- the standard Connect4 board and its nearest relatives (Connect4Game(board_size
+ * = nx, rows = ny); square boards are az_c4_trunk_fwd / az_c4n_trunk_fwd).  The network reads the
+ * board as a [1][nx][ny] image (Connect4Net.py:43), so the convolutions run with H = nx, W = ny and
+ * feature c * nx*ny + x * ny + y is channel c at column x, row y.  conv1 3x3 p1 + ReLU -> conv2 3x3
+ * p1 + ReLU -> NCHW flatten in ONE launch, one workgroup per board, conv1's plane and the feature
+ * row in LDS; feat is bit-identical to two az_conv3x3_relu_fwd(H = nx, W = ny) calls.
+ *   boards  int8 [B][nx][ny] in {-1,0,1} (may be az_host_alloc memory)
+ *   feat    fp32 [B][64 nx ny], 16-byte aligned; conv2_w 16-byte aligned */
+int az_c4r_trunk_fwd(const int8_t* boards, int B, int nx, int ny, const float* conv1_w,
+                     const float* conv1_b, const float* conv2_w, const float* conv2_b,
+                     float* feat, void* stream);
+/* The same launch followed, in the same workgroup, by the policy/value heads of the board's
+ * feature row read from LDS: ONE launch at every B, no workspace, bit-identical to
+ * az_c4r_trunk_fwd + az_heads_fwd(K = 64 nx ny).  feat may be NULL (the rows are then not
+ * stored); pi may be NULL; logp [B][A], v [B]; A <= 32. */
+int az_c4r_trunk_heads_fwd(const int8_t* boards, int B, int nx, int ny, const float* conv1_w,
+                           const float* conv1_b, const float* conv2_w, const float* conv2_b,
+                           const float* wp, const float* bp, int A, const float* wv,
+                           const float* bv, float* feat, float* logp, float* pi, float* v,
+                           void* stream);
+
+/* az_c4n_eval_fwd for the rectangular boards above: the whole leaf evaluation (predict and
+ * predict_with_gnn of the same boards) as ONE host call with direct launches --
+ * az_c4r_trunk_heads_fwd (the heads formed only when v is asked for, feat stored only for the GNN
+ * tail), then az_transform_heads_fwd(y = NULL) on feat.  One launch for v alone, four with gv.  At
+ * every B the outputs are bit-identical to az_conv3x3_relu_fwd x 2, az_heads_fwd and
+ * az_transform_heads_fwd(y = NULL) called one by one, and a row of a batch of <= 8 is
+ * bit-identical to the same board evaluated alone.  The fields are az_c4n_eval's with nx, ny in
+ * place of n. */
+typedef struct az_c4r_eval {
+  const float* conv1_w; const float* conv1_b; const float* conv2_w; const float* conv2_b;
+  const float* fc_policy_w; const float* fc_policy_b; const float* fc_value_w;
+  const float* fc_value_b;
+  int A;                                   /* actions (fc_policy rows), <= 32 */
+  const float* ot0_w; const float* ot0_b;  /* output_transform.0 [F][F], [F] */
+  const float* ot2_w; const float* ot2_b;  /* output_transform.2; all four NULL: no GNN tail */
+  int max_B;                               /* capacity of the scratch below */
+  float* feat; float* hidden; float* y;    /* device [max_B][F] (hidden: GNN only; y: not used,
+                                              may be NULL) */
+  float* logp; float* glogp;               /* device [max_B][A] */
+  void* ws; size_t ws_bytes;               /* GNN tail: >= az_c4r_eval_ws_bytes(max_B, nx, ny, A);
+                                              without one ws may be NULL */
+  int nx; int ny;                          /* columns, rows: (7, 6), (6, 5), (5, 4) or (8, 7) */
+  int F;                                   /* 64 nx ny */
+} az_c4r_eval;
+/* Workspace of a descriptor with a GNN tail (az_transform_heads_ws_bytes(max_B, 64 nx ny, A)).
+ * 0 for a shape az_c4r_eval_fwd rejects. */
+size_t az_c4r_eval_ws_bytes(int max_B, int nx, int ny, int A);
+/* v != NULL: standard heads into pi [B][A] (may be NULL) and v [B];  gv != NULL: the GNN tail
+ * into gpi / gv; at least one of them.  boards, pi, v, gpi, gv may be az_host_alloc memory.
+ * 1 <= B <= max_B.  A bad shape ((nx, ny) outside the four above -- a square (n, n) is named as
+ * az_c4_eval_fwd's or az_c4n_eval_fwd's board --, A > 32, F != 64 nx ny, B), a null pointer or a
+ * small workspace returns AZ_EINVAL before anything is launched. */
+int az_c4r_eval_fwd(const az_c4r_eval* e, const int8_t* boards, int B, float* pi, float* v,
+                    float* gpi, float* gv, void* stream);
+
 /* TicTacToeNet trunk, tictactoe/TicTacToeNet.py:33-36 (== TicTacToeGNNWrapper.extract_features,
  * TicTacToeGNN.py:25-34): conv1 3x3 p1 + ReLU -> conv2 3x3 p1 + ReLU -> conv3 3x3 p0 + ReLU ->
  * NCHW flatten in ONE launch, one workgroup per board, both intermediate planes in LDS.  Every

@@ -51,6 +51,12 @@ const char* az_mcts_last_error(void);
 /* An engine for `slots` concurrent games of one kind.  n*n <= 64.  cpuct as args.cpuct;
  * use_gnn selects the GNN outputs for priors and leaf values (MCTS.py:172-193). */
 az_mcts* az_mcts_create(int game, int n, int slots, double cpuct, int use_gnn);
+/* The same for a board of nx columns and ny rows, nx * ny <= 64: boards are int8 [nx][ny]
+ * (board[x][y], y counted from the bottom), cell x * ny + y, A = nx + 1 for Connect4.  nx == ny is
+ * az_mcts_create(game, nx, ...).  nx != ny is Connect4 only (Connect4Game(board_size = nx, rows =
+ * ny): 4 in a row, nx >= 4, ny >= 4); TicTacToe stays square.  Every other entry point takes the
+ * engine's shape from the handle. */
+az_mcts* az_mcts_create_rect(int game, int nx, int ny, int slots, double cpuct, int use_gnn);
 void az_mcts_destroy(az_mcts* m);
 int az_mcts_action_size(const az_mcts* m);
 
@@ -172,6 +178,12 @@ int az_rng_doubles(uint32_t seed, int n, double* out);
 int az_game_ended(int game, int n, const int8_t* board, int* tag, double* value);
 int az_game_valids(int game, int n, const int8_t* board, int8_t* valids);
 int az_game_next_canonical(int game, int n, const int8_t* board, int action, int8_t* out);
+/* The three probes on a board of nx columns and ny rows (int8 [nx][ny]; az_mcts_create_rect's
+ * shapes); the forms above are these with nx = ny = n. */
+int az_game_ended_rect(int game, int nx, int ny, const int8_t* board, int* tag, double* value);
+int az_game_valids_rect(int game, int nx, int ny, const int8_t* board, int8_t* valids);
+int az_game_next_canonical_rect(int game, int nx, int ny, const int8_t* board, int action,
+                                int8_t* out);
 /* The non-terminal canonical boards one move below a non-terminal `board` (valid actions in
  * ascending order, at most `cap`), written to out [cap][n*n]; returns their count (0 for a
  * terminal board).  The arena's speculative leaf batches use it (mcts_native.ArenaPlayer). */
