@@ -109,9 +109,26 @@ class Coach:
         self.nnet = nnet
         self.pnet = self.nnet.__class__(self.game, args)   # the competitor (Coach.py:21)
         self.args = args
+        if _flag(args, "gnn_neighbors"):
+            # the leaf's neighbourhood is built by the Python search (MCTS.evaluate_request):
+            # neither the native engine nor the lock-step drivers evaluate stars
+            parallel = int(_flag(args, "parallel_games", 1) or 1)
+            world = D.world_rank()[0]
+            if parallel > 1 or world > 1:
+                raise ValueError(
+                    "gnn_neighbors evaluates every leaf with its children on the sequential "
+                    f"Python search; it cannot be combined with parallel_games={parallel} > 1 or "
+                    f"a process group of {world} > 1 ranks")
         self.mcts = MCTS(self.game, self.nnet, self.args)
         self.trainExamplesHistory = []
         self.skipFirstSelfPlay = False
+
+    def uses_native_engine(self):
+        """Lock-step self-play and the arena run in the native engine when it is selected and
+        covers the game; args.gnn_neighbors keeps both on the Python search, the only one that
+        hands a leaf's children to predict_with_gnn."""
+        return (_flag(self.args, "selfplay_engine", "native") == "native"
+                and not _flag(self.args, "gnn_neighbors") and _native_ok(self.game))
 
     def executeEpisode(self):
         """Coach.py:27-79: one self-play game -> (std_examples, gnn_examples)."""
@@ -142,7 +159,7 @@ class Coach:
         base = D.broadcast_int(np.random.randint(0, 2 ** 31 - 1))
         seeds = episode_seeds(base, range(n))
         mine = D.my_episodes(n, world, rank)
-        if _flag(self.args, "selfplay_engine", "native") == "native" and _native_ok(self.game):
+        if self.uses_native_engine():
             local = play_episodes_engine(self.game, self.nnet, self.args, mine, seeds,
                                          parallel_games=max(1, parallel))
         else:
@@ -196,8 +213,7 @@ class Coach:
                 self.nnet.save_checkpoint(folder=self.args.checkpoint, filename=temp)
             self._barrier()
             self.pnet.load_checkpoint(folder=self.args.checkpoint, filename=temp)
-            native_arena = (_flag(self.args, "selfplay_engine", "native") == "native"
-                            and _native_ok(self.game))
+            native_arena = self.uses_native_engine()
             if native_arena:
                 from mcts_native import ArenaPlayer
                 pplayer = ArenaPlayer(self.game, self.pnet, self.args)

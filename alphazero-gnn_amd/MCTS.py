@@ -55,14 +55,32 @@ class MCTS:
     def _choice(self, *a, **k):
         return (np.random if self.rng is None else self.rng).choice(*a, **k)
 
+    def _gnn_neighbors(self):
+        return bool(getattr(self.args, "gnn_neighbors", False)) if not isinstance(self.args, dict) \
+            else bool(self.args.get("gnn_neighbors", False))
+
+    def leaf_children(self, board):
+        """The neighbourhood of a leaf for args.gnn_neighbors: the canonical next state of every
+        valid action in action order, stepped the way search_g steps (terminal children
+        included)."""
+        valids = self.game.getValidMoves(board, 1)
+        return [self.game.getCanonicalForm(*self.game.getNextState(board, 1, a))
+                for a in range(self.game.getActionSize()) if valids[a]]
+
     # ------------------------------------------------------------------ batch-1 driver
     def evaluate_request(self, request):
-        """Serve one leaf request with the reference's batch-1 calls (MCTS.py:169-174)."""
+        """Serve one leaf request with the reference's batch-1 calls (MCTS.py:169-174).  With
+        args.gnn_neighbors the GNN looks at the leaf's neighbourhood: predict_with_gnn receives
+        the leaf's children (leaf_children) as neighbor_states; with the flag off the call is
+        the reference's, one positional argument."""
         board, want_gnn = request
         std = gnn = err = None
         try:
             std = self.nnet.predict(board)
-            if want_gnn:
+            if want_gnn and self._gnn_neighbors():
+                gnn = self.nnet.predict_with_gnn(board,
+                                                 neighbor_states=self.leaf_children(board))
+            elif want_gnn:
                 gnn = self.nnet.predict_with_gnn(board)
         except Exception as e:  # handled where the reference handles it (search / expand_tree)
             err = e

@@ -85,6 +85,18 @@ class C4rEval(ctypes.Structure):
     _fields_ = C4Eval._fields_[:-2] + [("nx", c_int), ("ny", c_int), ("F", c_int)]
 
 
+STAR_MAX_NODES, STAR_MAX_STARS, STAR_MAX_LAYERS, STAR_HIDDEN = 9, 8, 4, 128
+
+
+class C4StarEval(ctypes.Structure):
+    """az_c4_star_eval (include/az_hip.h)."""
+    _fields_ = (C4Eval._fields_[:13] +
+                [("nx", c_int), ("ny", c_int), ("F", c_int), ("L", c_int),
+                 ("layers", LayerW * STAR_MAX_LAYERS), ("max_B", c_int), ("feat", c_void_p),
+                 ("x0", c_void_p), ("hidden", c_void_p), ("glogp", c_void_p), ("ws", c_void_p),
+                 ("ws_bytes", c_size_t)])
+
+
 class TttEval(ctypes.Structure):
     """az_ttt_eval (include/az_hip.h)."""
     _fields_ = ([(f"{l}_{k}", c_void_p) for l in ("conv1", "conv2", "conv3", "fc1", "fc2",
@@ -145,6 +157,12 @@ SIGNATURES = {
     "az_c4r_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "az_c4r_eval_fwd": (c_int, [ctypes.POINTER(C4rEval), c_void_p, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    "az_gnn_star_infer_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "az_gnn_star_infer": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                  ctypes.POINTER(LayerW), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "az_c4_star_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "az_c4_star_eval_fwd": (c_int, [ctypes.POINTER(C4StarEval), c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_void_p]),
     "az_ttt_trunk_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "az_ttt_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -248,6 +248,19 @@ class PolicyValueGNN(_Net):
             x = self.run_layers(x, self._star(x.shape[0]))
         return self.output_transform(x)
 
+    def star_rows0(self, x, counts):
+        """Row 0 of each of B <= 8 small stars after the layer stack in eval mode
+        (az_gnn_star_infer): x [B][nodes <= 9][F] features on HBM, star b = its first counts[b]
+        rows (row 0 the leaf, the rest its neighbours); counts a sequence or an int32 tensor.
+        Returns [B][F]; output_transform is the caller's (a row is then one row of
+        gnn_per_row_heads).  Each star's row is bit-identical to that star evaluated alone."""
+        self.params.sync()
+        if not isinstance(counts, torch.Tensor):
+            counts = torch.tensor(list(counts), dtype=torch.int32, device=x.device)
+        out, self._star_ws = ops.gnn_star_infer(x, counts, [l.weights() for l in self.layers],
+                                                ws=getattr(self, "_star_ws", None))
+        return out
+
     def forward_per_row(self, features):
         """Each row as its own 1-row input (batched predict_with_gnn semantics)."""
         return self.output_transform(features)

@@ -453,6 +453,85 @@ def c4r_eval(ev, boards_i8, B, pi=None, v=None, gpi=None, gv=None, stream=None):
                                           _p(gpi), _p(gv), s), "az_c4r_eval_fwd")
 
 
+STAR_MAX_NODES, STAR_MAX_STARS, STAR_MAX_LAYERS = (_lib.STAR_MAX_NODES, _lib.STAR_MAX_STARS,
+                                                   _lib.STAR_MAX_LAYERS)
+
+
+def star_shape_ok(shape):
+    """True for the (cols, rows) boards az_c4_star_eval_fwd has a fused trunk for."""
+    nx, ny = (int(s) for s in shape)
+    return (nx == ny and (nx == 7 or nx in C4N_SIDES)) or (nx, ny) in C4R_SHAPES
+
+
+def gnn_star_infer(x, counts, layers, out=None, ws=None, H=128):
+    """az_gnn_star_infer: x [B][nodes][F] (B <= 8 stars, row 0 the leaf, nodes <= 9 slots of which
+    star b uses the first counts[b]), counts int32 [B] (device tensor or HostBuffer view), layers a
+    list of GNNLayer weight dicts -> out [B][F], row 0 of every star after the layers in eval mode
+    (gnn_utils.py:34-74).  Returns (out, ws)."""
+    _need(x, name="x")
+    _need(counts, torch.int32, "counts")
+    B, nodes, F = x.shape
+    if x.stride(2) != 1 or x.stride(1) != F:
+        raise ValueError("gnn_star_infer: the rows of a star must be contiguous")
+    L = _lib.lib()
+    nl = len(layers)
+    nbytes = int(L.az_gnn_star_infer_ws_bytes(B, F, H, nl)) if B else 0
+    if B and nbytes == 0:
+        raise ValueError(f"az_gnn_star_infer: unsupported shape B={B} F={F} H={H} L={nl}")
+    dev = _dev(x)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    out = torch.empty((B, F), device=dev) if out is None else out
+    lw = (LayerW * max(nl, 1))(*[layer_weights(Wl) for Wl in layers])
+    _lib.check(L.az_gnn_star_infer(_p(x), x.stride(0), _p(counts), B, F, H, nl, lw, _p(out),
+                                   _p(ws), ctypes.c_size_t(ws.numel()), _stream()),
+               "az_gnn_star_infer")
+    return out, ws
+
+
+class C4StarEval:
+    """az_c4_star_eval descriptor with its device scratch for up to max_B <= 8 stars of <= 9 boards
+    of a cols x rows Connect4Net (`shape` with a fused trunk: star_shape_ok): W the net's parameter
+    tensors, G the PolicyValueGNN's, num_layers its GNNLayers.  The tensors are read through the
+    pointers taken here, so they must be updated in place."""
+
+    def __init__(self, W, G, shape, A, num_layers, max_B, device):
+        nx, ny = (int(s) for s in shape)
+        F = 64 * nx * ny
+        self.shape, self.A, self.F, self.L, self.max_B = (nx, ny), A, F, num_layers, max_B
+        nb = int(_lib.lib().az_c4_star_eval_ws_bytes(max_B, nx, ny, A, num_layers))
+        if nb == 0:
+            raise ValueError(f"az_c4_star_eval: unsupported shape cols={nx} rows={ny} A={A} "
+                             f"L={num_layers} max_B={max_B}")
+        e = lambda *s: torch.empty(s, device=device, dtype=torch.float32)  # noqa: E731
+        self.feat = e(max_B * STAR_MAX_NODES, F)
+        self.x0, self.hidden, self.glogp = e(max_B, F), e(max_B, F), e(max_B, A)
+        self.ws = torch.empty((nb,), dtype=torch.uint8, device=device)
+        P = lambda t: t.data_ptr()  # noqa: E731
+        d = self.desc = _lib.C4StarEval()
+        for l in ("conv1", "conv2", "fc_policy", "fc_value"):
+            for k in ("weight", "bias"):
+                setattr(d, f"{l}_{k[0]}", P(W[f"{l}.{k}"]))
+        for i in (0, 2):
+            for k in ("weight", "bias"):
+                setattr(d, f"ot{i}_{k[0]}", P(G[f"output_transform.{i}.{k}"]))
+        d.A, d.nx, d.ny, d.F, d.L, d.max_B = A, nx, ny, F, num_layers, max_B
+        for i in range(num_layers):
+            d.layers[i] = LayerW(*[P(G[f"layers.{i}.{k}"]) for k in LAYER_KEYS])
+        d.feat, d.x0, d.hidden, d.glogp = P(self.feat), P(self.x0), P(self.hidden), P(self.glogp)
+        d.ws, d.ws_bytes = P(self.ws), nb
+        self._keep = (W, G)
+
+
+def c4_star_eval(ev, boards_i8, counts, B, gpi=None, gv=None, stream=None):
+    """az_c4_star_eval_fwd on `ev` (a C4StarEval): the first B stars of boards_i8 [*, 9, cols,
+    rows] with counts int32 [*] -> gpi [B][A] (optional) and gv [B]; device tensors or HostBuffer
+    views.  Queued on `stream` (default: the current stream); nothing is synchronised."""
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(_lib.lib().az_c4_star_eval_fwd(ctypes.byref(ev.desc), _p(boards_i8), _p(counts), B,
+                                              _p(gpi), _p(gv), s), "az_c4_star_eval_fwd")
+
+
 def heads(hp, wp, bp, wv, bv, hv=None, want_pi=True, logp=None, pi=None, v=None):
     """logp = log_softmax(hp wp^T + bp); v = tanh(hv wv^T + bv) (hv defaults to hp)."""
     hv = hp if hv is None else hv

@@ -521,6 +521,51 @@ class _C4rBatch1Direct(_TttBatch1Direct):
         return (w.board_x, w.board_y)
 
 
+class _StarDirect:
+    """GNN evaluation of up to 8 leaves with their neighbourhoods (stars of <= 9 boards) as ONE C
+    call (az_c4_star_eval_fwd: the fused trunk, four launches per GNN layer, output_transform and
+    the heads) with zero-copy staging, like _C4rBatch1Direct: boards and counts are read and gpi /
+    gv written in place in mapped host memory.  A star's outputs are bit-identical to the same
+    star evaluated alone."""
+
+    cap = ops.STAR_MAX_STARS
+
+    def __init__(self, w):
+        dev, A, cap, N = w.device, w.action_size, self.cap, ops.STAR_MAX_NODES
+        hw = w.board_x * w.board_y
+        off = [0]
+        for nbytes in (cap * N * hw, 4 * cap, 4 * cap * A, 4 * cap):
+            off.append(off[-1] + (nbytes + 255) // 256 * 256)
+        self.host = ops.HostBuffer(off[-1])
+        self.h_in = self.host.view(off[0], torch.int8, (cap, N, w.board_x, w.board_y))
+        self.h_counts = self.host.view(off[1], torch.int32, (cap,))
+        self.h_pi = self.host.view(off[2], torch.float32, (cap, A))
+        self.h_v = self.host.view(off[3], torch.float32, (cap,))
+        self.h_in.zero_()
+        self.ev = ops.C4StarEval(w.nnet.params, w.gnn.params, (w.board_x, w.board_y), A,
+                                 w.gnn.num_layers, cap, dev)
+        self.in_np, self.counts_np = self.h_in.numpy(), self.h_counts.numpy()
+        self.pi_np, self.v_np = self.h_pi.numpy(), self.h_v.numpy()
+        self.fn = _lib.lib().az_c4_star_eval_fwd
+        P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        self.args = (ctypes.byref(self.ev.desc), P(self.h_in), P(self.h_counts))
+        self.outs = (P(self.h_pi), P(self.h_v))
+        self.stream = torch.cuda.current_stream(dev)
+        self.sptr = ctypes.c_void_p(self.stream.cuda_stream)
+
+    def run(self, node_lists):
+        """len(node_lists) <= 8 stars of <= 9 boards each -> (gpi [B][A], gv [B]) copies."""
+        B = len(node_lists)
+        for b, nodes in enumerate(node_lists):
+            self.counts_np[b] = len(nodes)
+            self.in_np[b, :len(nodes)] = nodes
+        rc = self.fn(*self.args, B, *self.outs, self.sptr)
+        if rc:
+            _lib.check(rc, "az_c4_star_eval_fwd")
+        self.stream.synchronize()
+        return self.pi_np[:B].copy(), self.v_np[:B].copy()
+
+
 def _c4_shape(w):
     """(columns, rows) of a Connect4Net wrapper's board, None for another network.  Both extents
     count: a 7-column board that is not 7 rows high is NOT the 7x7 board of az_c4_*."""
@@ -918,9 +963,81 @@ class GNNWrapperMixin:
     def predict(self, board):
         return NetWrapper.predict(self, board)
 
-    def predict_with_gnn(self, board):
-        """GNN-enhanced prediction: a 1-row input, so the message-passing layers are the
-        identity (gnn_utils.py:35-36) and only output_transform runs before the heads."""
+    def _star_direct_ok(self):
+        """The one-call star evaluator (az_c4_star_eval_fwd) serves Connect4 boards with a fused
+        trunk; AZ_B1_MODE=graph or AZ_NO_ZEROCOPY=1 select the composition, as they select the
+        older routes elsewhere."""
+        s = _c4_shape(self)
+        return (s is not None and ops.star_shape_ok(s)
+                and self.gnn.num_layers <= ops.STAR_MAX_LAYERS
+                and os.environ.get("AZ_B1_MODE", "direct") == "direct"
+                and os.environ.get("AZ_NO_ZEROCOPY", "0") in ("", "0"))
+
+    def _star_compose(self, node_lists):
+        """Any number of stars of any size on any wrapper: the trunk on every board, the layers on
+        a forest-of-stars graph through the generic graph calls, output_transform and the heads on
+        the row 0s.  No new kernel and no batch-invariance promise."""
+        counts = tuple(len(nodes) for nodes in node_lists)
+        boards = np.concatenate([np.asarray(nodes, dtype=np.int8).reshape(
+            len(nodes), self.board_x, self.board_y) for nodes in node_lists])
+        x = self.nnet.features(boards_to_device(boards, self.device))
+        starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+        if max(counts) > 1:
+            cache = self.__dict__.setdefault("_star_graphs", {})
+            g = cache.get(counts)
+            if g is None:
+                if len(cache) >= 64:
+                    cache.clear()
+                rowptr = np.full(sum(counts) + 1, 0, np.int64)
+                col, e = [], 0
+                for s, n in zip(starts, counts):
+                    rowptr[s] = e
+                    e += n - 1
+                    rowptr[s + 1:s + n + 1] = e
+                    col += list(range(s + 1, s + n))
+                g = cache[counts] = ops.DeviceGraph(rowptr, np.asarray(col, np.int64),
+                                                    self.device)
+            self.gnn.params.sync()
+            for layer in self.gnn.layers:
+                x, self.gnn._ws = ops.gnn_layer(g, x, layer.weights(), ws=self.gnn._ws,
+                                                save=False)
+        rows0 = x[torch.as_tensor(starts, device=self.device)].contiguous()
+        _, pi, v = nets.gnn_per_row_heads(self.nnet, self.gnn, rows0)
+        out = torch.cat([pi, v[:, None]], dim=1).cpu().numpy()
+        return out[:, :-1], out[:, -1]
+
+    def predict_star_batch(self, node_lists):
+        """GNN evaluation of B leaves with their neighbourhoods: node_lists[b] is the star
+        [board] + neighbor_states of leaf b (canonical boards, row 0 the leaf).  Returns
+        (gpi float32[B][A], gv float32[B]): the heads of row 0 after PolicyValueGNN.forward on
+        each star (Connect4GNN.py:86-120 on a star instead of a 1-row input).  Connect4 boards
+        with a fused trunk, <= 9 nodes and <= 8 stars take the one-call evaluator; everything
+        else the composition.  self.star_route names the route taken."""
+        self.nnet.eval()
+        self.gnn.eval()
+        self._sync_params()
+        A = self.action_size
+        if len(node_lists) == 0:
+            return np.zeros((0, A), np.float32), np.zeros((0,), np.float32)
+        if (self._star_direct_ok() and len(node_lists) <= ops.STAR_MAX_STARS
+                and max(len(nodes) for nodes in node_lists) <= ops.STAR_MAX_NODES):
+            d = self.__dict__.get("_star_direct")
+            if d is None:
+                d = self._star_direct = _StarDirect(self)
+            self.star_route = "onecall"
+            return d.run(node_lists)
+        self.star_route = "composition"
+        return self._star_compose(node_lists)
+
+    def predict_with_gnn(self, board, neighbor_states=None):
+        """GNN-enhanced prediction.  Without neighbours: a 1-row input, so the message-passing
+        layers are the identity (gnn_utils.py:35-36) and only output_transform runs before the
+        heads.  With `neighbor_states` (a list of canonical boards, Connect4Net.py:110): the star
+        [board] + neighbor_states goes through the layers and row 0 through the heads
+        (predict_star_batch)."""
+        if neighbor_states is not None and len(neighbor_states) > 0:
+            pi, v = self.predict_star_batch([[board] + list(neighbor_states)])
+            return pi[0], v[0]
         self.nnet.eval()
         self.gnn.eval()
         g = self._graph1("gnn")

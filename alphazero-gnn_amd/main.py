@@ -11,6 +11,8 @@ YAML (main.py:217-218), the three numeric overrides only when given.  Checkpoint
 MI355X additions (absent from the reference; defaults reproduce its behaviour):
     --parallel_games G       lock-step batched self-play with G concurrent games (selfplay.py)
     --train_parallel MODE    "replicas" | "allreduce" (azhip/dist.py) under torch.distributed
+    --gnn_neighbors          the GNN evaluates a leaf with its children as neighbours (MCTS.py);
+                             config key gnn_neighbors, sequential Python search only
     multi-GPU: python -m torch.distributed.run --nproc-per-node P --master-addr 127.0.0.1 main.py ...
                (one rank per GPU, backend nccl = RCCL; episodes sharded by index)
 """
@@ -135,6 +137,9 @@ def parse(argv=None):
     p.add_argument("--numMCTSSims", type=int)
     p.add_argument("--parallel_games", type=int, default=None)
     p.add_argument("--train_parallel", choices=["replicas", "allreduce"], default=None)
+    p.add_argument("--gnn_neighbors", action="store_true", default=None,
+                   help="with --use_gnn: the GNN evaluates every leaf together with its children "
+                        "(sequential Python search only)")
     return p.parse_args(argv)
 
 
@@ -154,7 +159,7 @@ def build_args(a):
         sys.exit(1)
     args = config_to_args(config)
     for k in ("board_size", "board_rows", "numIters", "numMCTSSims", "parallel_games",
-              "train_parallel"):
+              "train_parallel", "gnn_neighbors"):
         if getattr(a, k) is not None:
             args[k] = getattr(a, k)
     args.use_gnn = a.use_gnn

@@ -578,6 +578,75 @@ int az_mlp2_fwd(const float* x, int M, int F, const float* w0, const float* b0,
                 void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * GNN leaf evaluation over the leaf's children.  The reference's GNNLayer.forward is written for
+ * "row 0 is the target state, the other rows are path states" (gnn_utils.py:38-43), and
+ * Connect4Net.predict documents `neighbor_states` as an "optional list of neighboring states for GNN
+ * enhancement" (Connect4Net.py:110); FrozenLakeNet.predict builds that neighbourhood, the board plus
+ * the next state of every valid action.  These entry points evaluate such stars at inference.
+ * --------------------------------------------------------------------------------- */
+#define AZ_STAR_MAX_NODES 9    /* a leaf and up to 8 children */
+#define AZ_STAR_MAX_STARS 8
+#define AZ_STAR_MAX_LAYERS 4
+#define AZ_STAR_HIDDEN 128     /* attention.0's hidden width in the networks (gnn_utils.py:12) */
+/* The layer stack of PolicyValueGNN in eval mode (gnn_utils.py:34-74, 109-112) on B small stars.
+ *   x       star b: counts[b] rows of F floats at x + b * ldstar; row 0 the leaf, rows 1.. its
+ *           neighbours in the caller's order.  Rows at or beyond counts[b] are never read.
+ *   counts  int [B], mapped host memory or HBM; the kernels clamp a value into [1, 9] themselves
+ *   x0      [B][F]: row 0 of each star after L layers (only row 0 changes in a layer, so no other
+ *           row is written anywhere).  May not alias x.
+ * A one-row star passes unchanged, x0[b] = x[b][0] bit for bit (gnn_utils.py:35-36).  The weights
+ * are sigmoid(attention(.)) and are divided by their sum only when the sum is > 0
+ * (gnn_utils.py:58-59): with every weight underflowed to 0 the aggregate is 0.
+ * Four launches per layer: attention.0 factored per node (W1 [t; x] = W1[:, :F] t + W1[:, F:] x)
+ * with blocks that own 16 hidden units x 256 columns of one star, so its weights come from HBM
+ * once and not once per node; the attention weights and the aggregate per star; gate.0 and update_net.0 on
+ * [t; agg] as one paired GEMV grid over the B row 0s; update_net.2 with the gated residual
+ * t + g * u.  Every output is a fixed-order fp32 fmaf chain, no atomics, nothing shared between
+ * stars: star b's row does not depend on B or on the other stars of the call, and two calls give
+ * equal bits.
+ * 1 <= B <= 8 (B == 0: nothing to do), F % 4 == 0, H % 2 == 0, 0 <= L <= 4, ldstar >= F and
+ * ldstar % 4 == 0; x, x0, ws and the weight matrices 16-byte aligned; anything else returns
+ * AZ_EINVAL with a message before any launch.  ws >= az_gnn_star_infer_ws_bytes(B, F, H, L)
+ * (0 for a rejected shape). */
+size_t az_gnn_star_infer_ws_bytes(int B, int F, int H, int L);
+int az_gnn_star_infer(const float* x, int ldstar, const int* counts, int B, int F, int H, int L,
+                      const az_gnn_layer_w* layers, float* x0, void* ws, size_t ws_bytes,
+                      void* stream);
+
+/* predict_with_gnn of a Connect4 leaf with its neighbourhood (Connect4GNN.py:86-120 on the star
+ * [board] + neighbor_states: extract_features, PolicyValueGNN.forward, the heads of row 0) as ONE
+ * host call with direct launches: the board's fused trunk (az_c4_trunk_fwd for 7x7,
+ * az_c4n_trunk_fwd for 4x4, 5x5, 6x6 and 8x8, az_c4r_trunk_fwd for 7x6, 6x5, 5x4 and 8x7) on the
+ * 9 board slots of every star, az_gnn_star_infer on the feature rows, then
+ * az_transform_heads_fwd(y = NULL) on the B row 0s.  Another board shape returns AZ_EINVAL. */
+typedef struct az_c4_star_eval {
+  const float* conv1_w; const float* conv1_b; const float* conv2_w; const float* conv2_b;
+  const float* fc_policy_w; const float* fc_policy_b; const float* fc_value_w;
+  const float* fc_value_b;
+  int A;                                   /* actions (fc_policy rows), <= 32 */
+  const float* ot0_w; const float* ot0_b;  /* output_transform.0 [F][F], [F] */
+  const float* ot2_w; const float* ot2_b;  /* output_transform.2 */
+  int nx; int ny;                          /* columns, rows */
+  int F;                                   /* 64 nx ny */
+  int L;                                   /* GNN layers, 0..4 */
+  az_gnn_layer_w layers[AZ_STAR_MAX_LAYERS];   /* entries >= L unused */
+  int max_B;                               /* most stars one call may carry, <= 8 */
+  float* feat;                             /* device [max_B * 9][F] */
+  float* x0; float* hidden;                /* device [max_B][F] each */
+  float* glogp;                            /* device [max_B][A] */
+  void* ws; size_t ws_bytes;               /* >= az_c4_star_eval_ws_bytes(max_B, nx, ny, A, L) */
+} az_c4_star_eval;
+/* 0 for a shape az_c4_star_eval_fwd rejects. */
+size_t az_c4_star_eval_ws_bytes(int max_B, int nx, int ny, int A, int L);
+/* boards int8 [B][9][nx ny] in the project's [column][row] order (slot i of star b is its row i; a
+ * slot at or beyond counts[b] may hold anything: its features are never read), counts int [B],
+ * gpi [B][A] (may be NULL), gv [B].  boards, counts, gpi and gv may be az_host_alloc memory.
+ * 0 <= B <= min(max_B, 8) (0: nothing to do).  A row is bit-identical to the same star evaluated
+ * alone.  A bad shape, a null pointer or a small workspace returns AZ_EINVAL before any launch. */
+int az_c4_star_eval_fwd(const az_c4_star_eval* e, const int8_t* boards, const int* counts, int B,
+                        float* gpi, float* gv, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Backward pass (Connect4GNN.py:150-156,187-197 / TicTacToeGNN.py:217-264), deterministic:
  * every reduction runs in a fixed order, no float atomics.
  * --------------------------------------------------------------------------------- */
