@@ -109,9 +109,14 @@ class Coach:
         self.nnet = nnet
         self.pnet = self.nnet.__class__(self.game, args)   # the competitor (Coach.py:21)
         self.args = args
-        if _flag(args, "gnn_neighbors"):
-            # the leaf's neighbourhood is built by the Python search (MCTS.evaluate_request):
-            # neither the native engine nor the lock-step drivers evaluate stars
+        lockstep = bool(_flag(args, "gnn_neighbors_lockstep"))
+        if lockstep and not (_flag(args, "use_gnn") and _flag(args, "gnn_neighbors")):
+            raise ValueError("gnn_neighbors_lockstep batches the star evaluation of gnn_neighbors: "
+                             "it needs both use_gnn and gnn_neighbors")
+        if _flag(args, "gnn_neighbors") and not lockstep:
+            # the leaf's neighbourhood is built by the Python search (MCTS.evaluate_request);
+            # without gnn_neighbors_lockstep neither the native engine nor the lock-step drivers
+            # evaluate stars
             parallel = int(_flag(args, "parallel_games", 1) or 1)
             world = D.world_rank()[0]
             if parallel > 1 or world > 1:
@@ -129,6 +134,15 @@ class Coach:
         hands a leaf's children to predict_with_gnn."""
         return (_flag(self.args, "selfplay_engine", "native") == "native"
                 and not _flag(self.args, "gnn_neighbors") and _native_ok(self.game))
+
+    def selfplay_uses_native_engine(self):
+        """Self-play's own predicate: as uses_native_engine, and also under gnn_neighbors once
+        gnn_neighbors_lockstep is set (the engine lanes build every round's stars natively and
+        make one predict_both_stars call; the arena stays on the Python search)."""
+        return (_flag(self.args, "selfplay_engine", "native") == "native"
+                and (not _flag(self.args, "gnn_neighbors")
+                     or bool(_flag(self.args, "gnn_neighbors_lockstep")))
+                and _native_ok(self.game))
 
     def executeEpisode(self):
         """Coach.py:27-79: one self-play game -> (std_examples, gnn_examples)."""
@@ -159,7 +173,7 @@ class Coach:
         base = D.broadcast_int(np.random.randint(0, 2 ** 31 - 1))
         seeds = episode_seeds(base, range(n))
         mine = D.my_episodes(n, world, rank)
-        if self.uses_native_engine():
+        if self.selfplay_uses_native_engine():
             local = play_episodes_engine(self.game, self.nnet, self.args, mine, seeds,
                                          parallel_games=max(1, parallel))
         else:

@@ -489,6 +489,44 @@ def gnn_star_infer(x, counts, layers, out=None, ws=None, H=128):
     return out, ws
 
 
+def gnn_star_batch_ws_bytes(B, V, F, num_layers, H=128):
+    """az_gnn_star_batch_ws_bytes (no GPU work)."""
+    return int(_lib.load().az_gnn_star_batch_ws_bytes(B, V, F, H, num_layers))
+
+
+def gnn_star_batch_infer(x, offs, layers, out=None, ws=None, H=128, stream=None):
+    """az_gnn_star_batch_infer: x [V][F] packed star rows, offs int32 [B+1] (device tensor or
+    HostBuffer view; star b = rows offs[b] .. offs[b+1]-1, row 0 the leaf), layers a list of
+    GNNLayer weight dicts (or a prepared LayerW array) -> out [B][F], row 0 of every star after the
+    layers in eval mode (gnn_utils.py:34-74).  Any number of stars of any size.  Returns
+    (out, ws)."""
+    _need(x, name="x")
+    _need(offs, torch.int32, "offs")
+    V, F = x.shape
+    B = offs.numel() - 1
+    if not x.is_contiguous():
+        raise ValueError("gnn_star_batch_infer: x must be contiguous")
+    L = _lib.lib()
+    if isinstance(layers, ctypes.Array):
+        lw, nl = layers, len(layers)
+    else:
+        nl = len(layers)
+        lw = (LayerW * max(nl, 1))(*[layer_weights(Wl) for Wl in layers])
+    nbytes = int(L.az_gnn_star_batch_ws_bytes(B, V, F, H, nl)) if B > 0 else 0
+    if B > 0 and nbytes == 0:
+        raise ValueError(f"az_gnn_star_batch_infer: unsupported shape B={B} V={V} F={F} H={H} "
+                         f"L={nl}")
+    dev = _dev(x)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    out = torch.empty((max(B, 0), F), device=dev) if out is None else out
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(L.az_gnn_star_batch_infer(_p(x), _p(offs), B, V, F, H, nl, lw, _p(out), _p(ws),
+                                         ctypes.c_size_t(ws.numel()), s),
+               "az_gnn_star_batch_infer")
+    return out, ws
+
+
 class C4StarEval:
     """az_c4_star_eval descriptor with its device scratch for up to max_B <= 8 stars of <= 9 boards
     of a cols x rows Connect4Net (`shape` with a fused trunk: star_shape_ok): W the net's parameter

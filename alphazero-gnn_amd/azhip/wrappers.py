@@ -566,6 +566,147 @@ class _StarDirect:
         return self.pi_np[:B].copy(), self.v_np[:B].copy()
 
 
+# Device bytes one chunk of predict_both_stars may hold in the buffers that grow with the batch.
+# Per packed row: its features (4 F) and, in az_gnn_star_batch_infer's workspace, the fp16 planes
+# of the projection GEMM's A operand (4 F) and its P row (2 H 4 = 1 KB); per star: TA (8 F), gate,
+# u1, the next row 0, the leaf row and x0 (4 F each) and its Pt row; fixed: the 40 MB of split-K
+# slabs plus ~2 MB of scales.  At F = 3136 that is 26 KB per row and 88 KB per star, so 1 GiB
+# holds about 4,000 stars of 9 boards: a 2,048-game lock-step round is one chunk.
+STAR_CHUNK_BYTES = 1 << 30
+
+
+def _star_chunk_cost(F):
+    """(bytes per packed row, bytes per star, fixed bytes) of STAR_CHUNK_BYTES' derivation."""
+    return 8 * F + 1024 + 64, 28 * F + 1024 + 64, 42 << 20
+
+
+def star_chunks(offs, F, budget=None):
+    """Split B stars (offs int [B+1]) into consecutive runs [b0, b1) whose buffers stay under the
+    budget (STAR_CHUNK_BYTES); a run is at least one star."""
+    budget = STAR_CHUNK_BYTES if budget is None else budget
+    cr, cs, fixed = _star_chunk_cost(F)
+    B = len(offs) - 1
+    lin = cr * np.asarray(offs, np.int64) + cs * np.arange(B + 1, dtype=np.int64)
+    out, b0 = [], 0
+    while b0 < B:
+        b1 = int(np.searchsorted(lin, lin[b0] + budget - fixed, side="right")) - 1
+        b1 = min(B, max(b1, b0 + 1))
+        out.append((b0, b1))
+        b0 = b1
+    return out
+
+
+class _StarBatch:
+    """predict_both_stars for one stream: packed stars in mapped host memory (ops.HostBuffer, a
+    ring so that several batches can be in flight), the trunk on all V rows, the standard heads on
+    the B leaf rows, az_gnn_star_batch_infer, output_transform + heads on the row 0s, outputs
+    written in place in mapped host memory.  Feature rows, row 0s and the workspace are allocated
+    once per capacity (small head temporaries come from torch's caching allocator); a batch whose
+    buffers would exceed STAR_CHUNK_BYTES runs as consecutive chunks on the same scratch."""
+
+    def __init__(self, w, stream=None):
+        self.w, self.stream = w, stream
+        self.capV = self.capB = 0
+        self.ring = []
+        if w.gnn.num_layers > ops.STAR_MAX_LAYERS:
+            raise ValueError(f"predict_both_stars: {w.gnn.num_layers} GNN layers > "
+                             f"{ops.STAR_MAX_LAYERS} (az_gnn_star_batch_infer)")
+
+    def _grow(self, V, B):
+        w, dev, F = self.w, self.w.device, self.w.feature_dim
+        capV = max(self.capV, (V + 1023) // 1024 * 1024)
+        capB = max(self.capB, (B + 255) // 256 * 256)
+        torch.cuda.synchronize(dev)               # in-flight batches may use the old scratch
+        self.feat = torch.empty((capV, F), device=dev)
+        self.leaf = torch.empty((capB, F), device=dev)
+        self.x0 = torch.empty((capB, F), device=dev)
+        nl = w.gnn.num_layers
+        nb = ops.gnn_star_batch_ws_bytes(capB, capV, F, nl)
+        if nb == 0:
+            raise ValueError(f"az_gnn_star_batch_infer: unsupported shape B={capB} V={capV} F={F}")
+        self.ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
+        self.layers = (ops.LayerW * max(nl, 1))(*[ops.layer_weights(l.weights())
+                                                  for l in w.gnn.layers])
+        # the heads' GEMMs take this stream's own workspace (the shared one would be written by
+        # two lanes' streams at once)
+        L, A = _lib.lib(), w.action_size
+        hb = max(int(L.az_transform_heads_ws_bytes(capB, F, A)),
+                 int(L.az_heads_ws_bytes(capB, F, A)), 64 << 20)
+        self.hws = torch.empty((hb,), dtype=torch.uint8, device=dev)
+        self.capV, self.capB = capV, capB
+
+    def _entry(self, V, B):
+        """A host staging set no unread prediction holds, large enough for V rows / B stars."""
+        for e in self.ring:
+            if not e["busy"] and e["V"] >= V and e["B"] >= B:
+                return e
+        self.ring = [e for e in self.ring if e["busy"]]   # too small and idle: dropped
+        w, A = self.w, self.w.action_size
+        cV, cB = (V + 1023) // 1024 * 1024, (B + 255) // 256 * 256
+        off = [0]
+        for nbytes in (cV * w.board_x * w.board_y, 4 * (2 * cB + 2), 4 * cB * A, 4 * cB,
+                       4 * cB * A, 4 * cB):
+            off.append(off[-1] + (nbytes + 255) // 256 * 256)
+        hb = ops.HostBuffer(off[-1])
+        e = {"busy": False, "hb": hb, "V": cV, "B": cB,
+             "in": hb.view(off[0], torch.int8, (cV, w.board_x, w.board_y)),
+             "offs": hb.view(off[1], torch.int32, (2 * cB + 2,)),
+             "out": [hb.view(off[2 + j], torch.float32, (cB, k) if k > 1 else (cB,))
+                     for j, k in enumerate((A, 1, A, 1))]}
+        self.ring.append(e)
+        return e
+
+    def _features(self, b, out):
+        """The wrapper's batched feature path into `out`: a fused trunk where the board has one,
+        the conv launches otherwise."""
+        net = self.w.nnet
+        W = net.params
+        if isinstance(net, nets.Connect4Net):
+            fn = {"c4": ops.c4_trunk, "c4n": ops.c4n_trunk, "c4r": ops.c4r_trunk}.get(net.route)
+            if fn is not None:
+                return fn(b, W, out=out)
+        elif isinstance(net, nets.TicTacToeNet) and 3 <= net.n <= 5:
+            return ops.ttt_trunk(b, W, out=out)
+        out.copy_(net.features(b))
+        return out
+
+    def launch(self, rows, offs):
+        w, F, A = self.w, self.w.feature_dim, self.w.action_size
+        rows = np.asarray(rows)
+        offs = np.asarray(offs, dtype=np.int64)
+        B, V = len(offs) - 1, int(offs[-1])
+        if B < 1 or offs[0] != 0 or V != rows.shape[0] or np.any(np.diff(offs) < 1):
+            raise ValueError("predict_both_stars: offs must ascend from 0 to len(rows), one or "
+                             "more rows per star")
+        chunks = star_chunks(offs, F, STAR_CHUNK_BYTES)
+        mV = max(int(offs[b1] - offs[b0]) for b0, b1 in chunks)
+        mB = max(b1 - b0 for b0, b1 in chunks)
+        if mV > self.capV or mB > self.capB:
+            self._grow(mV, mB)
+        e = self._entry(V, B)
+        hin, hoffs, (pi, v, gpi, gv) = e["in"], e["offs"], e["out"]
+        hin.numpy()[:V] = rows
+        ho = hoffs.numpy()
+        s = self.stream if self.stream is not None else torch.cuda.current_stream(w.device)
+        nl = w.gnn.num_layers
+        with torch.cuda.stream(s), ops.pinned_workspace(w.device, self.hws):
+            for c, (b0, b1) in enumerate(chunks):
+                v0, v1, n = int(offs[b0]), int(offs[b1]), b1 - b0
+                o0 = b0 + c                       # this chunk's rebased offs in the host buffer
+                ho[o0:o0 + n + 1] = offs[b0:b1 + 1] - v0
+                co = hoffs[o0:o0 + n + 1]
+                feat = self._features(hin[v0:v1], self.feat[:v1 - v0])
+                # the leaf rows (the layer stack at L = 0 is the gather of every star's row 0)
+                ops.gnn_star_batch_infer(feat, co, [], out=self.leaf[:n], ws=self.ws, stream=s)
+                w.nnet.heads(self.leaf[:n], pi=pi[b0:b1], v=v[b0:b1])
+                ops.gnn_star_batch_infer(feat, co, self.layers if nl else [], out=self.x0[:n],
+                                         ws=self.ws, stream=s)
+                nets.gnn_per_row_heads(w.nnet, w.gnn, self.x0[:n], pi=gpi[b0:b1], v=gv[b0:b1])
+        ev = torch.cuda.Event()
+        ev.record(s)
+        return _PendingDirect(e, (pi, v, gpi, gv), ev, B)
+
+
 def _c4_shape(w):
     """(columns, rows) of a Connect4Net wrapper's board, None for another network.  Both extents
     count: a 7-column board that is not 7 rows high is NOT the 7x7 board of az_c4_*."""
@@ -1011,23 +1152,68 @@ class GNNWrapperMixin:
         [board] + neighbor_states of leaf b (canonical boards, row 0 the leaf).  Returns
         (gpi float32[B][A], gv float32[B]): the heads of row 0 after PolicyValueGNN.forward on
         each star (Connect4GNN.py:86-120 on a star instead of a 1-row input).  Connect4 boards
-        with a fused trunk, <= 9 nodes and <= 8 stars take the one-call evaluator; everything
-        else the composition.  self.star_route names the route taken."""
+        with a fused trunk, <= 9 nodes and <= 8 stars take the one-call evaluator ("onecall",
+        today's bits).  Under args.gnn_neighbors_lockstep -- the opt-in key of the batched mode;
+        without it every route is what it was -- more than 8 stars, or a star of more than 9
+        nodes, takes predict_both_stars on every wrapper ("batched").  What is left takes the
+        composition (<= 8 small stars on another wrapper, or under AZ_B1_MODE=graph /
+        AZ_NO_ZEROCOPY=1; without the key also every larger batch).  Under the key those two
+        switches select nothing above 8 stars: measured end to end at 16 .. 2,048 stars of 8 nodes
+        on 7x7, 7x6 and 4x4, the batched route beat the composition 1.17x - 3.4x, everywhere by
+        more than the larger spread.  self.star_route names the route
+        taken."""
         self.nnet.eval()
         self.gnn.eval()
         self._sync_params()
         A = self.action_size
         if len(node_lists) == 0:
             return np.zeros((0, A), np.float32), np.zeros((0,), np.float32)
-        if (self._star_direct_ok() and len(node_lists) <= ops.STAR_MAX_STARS
-                and max(len(nodes) for nodes in node_lists) <= ops.STAR_MAX_NODES):
+        small = (len(node_lists) <= ops.STAR_MAX_STARS
+                 and max(len(nodes) for nodes in node_lists) <= ops.STAR_MAX_NODES)
+        if self._star_direct_ok() and small:
             d = self.__dict__.get("_star_direct")
             if d is None:
                 d = self._star_direct = _StarDirect(self)
             self.star_route = "onecall"
             return d.run(node_lists)
+        if (not small and self.gnn.num_layers <= ops.STAR_MAX_LAYERS
+                and nets._args_get(self.args, "gnn_neighbors_lockstep", False)):
+            self.star_route = "batched"
+            rows = np.concatenate([np.asarray(nodes, dtype=np.int8).reshape(
+                len(nodes), self.board_x, self.board_y) for nodes in node_lists])
+            offs = np.concatenate([[0], np.cumsum([len(nodes) for nodes in node_lists])])
+            _, _, gpi, gv = self.predict_both_stars(rows, offs.astype(np.int32))
+            return gpi, gv
         self.star_route = "composition"
         return self._star_compose(node_lists)
+
+    def _star_batch(self, stream=None):
+        batches = self.__dict__.setdefault("_star_batches", {})
+        key = None if stream is None else stream.cuda_stream
+        d = batches.get(key)
+        if d is None:
+            d = batches[key] = _StarBatch(self, stream)
+        return d
+
+    def predict_both_stars_async(self, rows, offs, stream=None):
+        """predict_both_stars without waiting: .result() -> (pi, v, gnn_pi, gnn_v).  stream: run
+        on that HIP stream with its own device scratch (the lock-step lanes give each lane one);
+        the caller orders the stream after any parameter update."""
+        self.nnet.eval()
+        self.gnn.eval()
+        self._sync_params()
+        return self._star_batch(stream).launch(rows, offs)
+
+    def predict_both_stars(self, rows, offs):
+        """Standard and GNN predictions of B leaves with their neighbourhoods, the batched form of
+        predict + predict_with_gnn(board, neighbor_states=...): rows int8 [V][cols][rows] packed
+        stars, offs int32 [B+1] (star b = rows offs[b] .. offs[b+1]-1, row 0 the leaf; the layout
+        of az_game_stars_rect).  One trunk pass over the V rows, the standard heads on the B leaf
+        rows, az_gnn_star_batch_infer, output_transform and the heads on the row 0s; one host copy
+        out -> (pi [B][A], v [B], gnn_pi [B][A], gnn_v [B]).  Rows are within 1e-5 of the
+        batch-1 calls, not bit-identical to them, and a batch split by STAR_CHUNK_BYTES may differ
+        in bits from the unsplit one (the GEMM dispatch chooses its tile by the row count)."""
+        return self.predict_both_stars_async(rows, offs).result()
 
     def predict_with_gnn(self, board, neighbor_states=None):
         """GNN-enhanced prediction.  Without neighbours: a 1-row input, so the message-passing

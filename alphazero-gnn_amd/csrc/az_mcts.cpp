@@ -1654,6 +1654,55 @@ int az_game_children(int game, int n, const int8_t* board, int cap, int8_t* out)
   return cnt;
 }
 
+int az_game_stars_rect(int game, int nx, int ny, const int8_t* boards, int count, int threads,
+                       int8_t* out, int32_t* offs, int cap_rows) {
+  Rules R;
+  if (!R.init(game, nx, ny) || count < 0 || cap_rows < 0 || !offs ||
+      (count > 0 && (!boards || !out)))
+    return fail(AZM_EINVAL, "az_game_stars_rect: bad args");
+  const int cells = R.cells, A = R.A;
+  threads = std::max(1, std::min(threads, 64));
+  // pass 1: keys and row counts (1 + valid actions); nothing is written before the sizes are known
+  std::vector<Key> keys(count);
+  std::vector<int32_t> start(count + 1, 0);
+  int bad = 0;
+#pragma omp parallel for schedule(static) num_threads(threads) if (count >= 64) reduction(+ : bad)
+  for (int i = 0; i < count; ++i) {
+    if (!R.from_board(boards + (size_t)i * cells, &keys[i])) {
+      ++bad;
+      continue;
+    }
+    uint8_t v[65];
+    R.valids(keys[i], v);
+    int n = 1;
+    for (int a = 0; a < A; ++a) n += v[a] ? 1 : 0;
+    start[i + 1] = n;
+  }
+  if (bad) return fail(AZM_EINVAL, "az_game_stars_rect: cells must be -1/0/1");
+  for (int i = 0; i < count; ++i) start[i + 1] += start[i];
+  if (start[count] > cap_rows)
+    return fail(AZM_EINVAL, "az_game_stars_rect: " + std::to_string(start[count]) +
+                                " rows do not fit cap_rows = " + std::to_string(cap_rows));
+  // pass 2: the leaf, then getCanonicalForm(getNextState(board, 1, a)) per valid action, ascending
+  // (terminal children included: MCTS.leaf_children)
+#pragma omp parallel for schedule(static) num_threads(threads) if (count >= 64)
+  for (int i = 0; i < count; ++i) {
+    int8_t* row = out + (size_t)start[i] * cells;
+    std::memcpy(row, boards + (size_t)i * cells, cells);
+    uint8_t v[65];
+    R.valids(keys[i], v);
+    Key nk;
+    for (int a = 0; a < A; ++a) {
+      if (!v[a]) continue;
+      row += cells;
+      if (R.next(keys[i], a, &nk)) R.to_board(nk, row);
+      else std::memset(row, 0, cells);          // unreachable: a valid action always steps
+    }
+  }
+  std::memcpy(offs, start.data(), sizeof(int32_t) * (count + 1));
+  return start[count];
+}
+
 double az_np_pairwise_sum(const double* a, int n) { return pairwise(a, n); }
 
 }  // extern "C"

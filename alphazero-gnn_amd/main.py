@@ -13,6 +13,10 @@ MI355X additions (absent from the reference; defaults reproduce its behaviour):
     --train_parallel MODE    "replicas" | "allreduce" (azhip/dist.py) under torch.distributed
     --gnn_neighbors          the GNN evaluates a leaf with its children as neighbours (MCTS.py);
                              config key gnn_neighbors, sequential Python search only
+    --gnn_neighbors_lockstep with --use_gnn --gnn_neighbors: self-play evaluates a round's leaves
+                             with their children in ONE batched star call (selfplay.py), so
+                             --parallel_games > 1 and several ranks are allowed; config key
+                             gnn_neighbors_lockstep
     multi-GPU: python -m torch.distributed.run --nproc-per-node P --master-addr 127.0.0.1 main.py ...
                (one rank per GPU, backend nccl = RCCL; episodes sharded by index)
 """
@@ -140,6 +144,9 @@ def parse(argv=None):
     p.add_argument("--gnn_neighbors", action="store_true", default=None,
                    help="with --use_gnn: the GNN evaluates every leaf together with its children "
                         "(sequential Python search only)")
+    p.add_argument("--gnn_neighbors_lockstep", action="store_true", default=None,
+                   help="with --use_gnn --gnn_neighbors: lock-step self-play with one batched star "
+                        "evaluation per round (allows --parallel_games > 1 and several ranks)")
     return p.parse_args(argv)
 
 
@@ -159,7 +166,7 @@ def build_args(a):
         sys.exit(1)
     args = config_to_args(config)
     for k in ("board_size", "board_rows", "numIters", "numMCTSSims", "parallel_games",
-              "train_parallel", "gnn_neighbors"):
+              "train_parallel", "gnn_neighbors", "gnn_neighbors_lockstep"):
         if getattr(a, k) is not None:
             args[k] = getattr(a, k)
     args.use_gnn = a.use_gnn

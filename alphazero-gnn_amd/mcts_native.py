@@ -69,6 +69,8 @@ _SIGS = {
     "az_game_next_canonical_rect": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P,
                                                    ctypes.c_int, _P]),
     "az_game_children": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _P, ctypes.c_int, _P]),
+    "az_game_stars_rect": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, _P,
+                                          ctypes.c_int, ctypes.c_int, _P, _P, ctypes.c_int]),
     "az_np_pairwise_sum": (ctypes.c_double, [_P, ctypes.c_int]),
     "az_mcts_episode_begin": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_uint32, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int]),
@@ -135,6 +137,26 @@ def game_kind(game):
     ValueError for anything else and for more than 64 cells."""
     kind, shape = game_shape(game)
     return kind, shape[0]
+
+
+def game_stars(kind, shape, boards, threads=1, cap_rows=None):
+    """az_game_stars_rect: boards int8 [count][cols][rows] (canonical, non-terminal) ->
+    (rows int8 [V][cols][rows], offs int32 [count+1]): star i = rows offs[i] .. offs[i+1]-1 = the
+    board, then the canonical next state of every valid action in action order, terminal children
+    included -- [board] + MCTS.leaf_children(board).  cap_rows (default: always enough) bounds the
+    rows; too few raise before anything is written."""
+    boards = np.ascontiguousarray(boards, dtype=np.int8)
+    nx, ny = int(shape[0]), int(shape[1])
+    count = boards.shape[0] if boards.ndim == 3 else 0
+    if boards.size and tuple(boards.shape[1:]) != (nx, ny):
+        raise ValueError(f"game_stars: boards of shape {boards.shape}, need [count, {nx}, {ny}]")
+    A = nx + 1 if kind == GAME_CONNECT4 else nx * ny + 1
+    cap = count * (A + 1) if cap_rows is None else int(cap_rows)
+    out = np.empty((max(cap, 1), nx, ny), np.int8)
+    offs = np.zeros(count + 1, np.int32)
+    V = _check(lib().az_game_stars_rect(kind, nx, ny, _ptr(boards), count, int(threads),
+                                        _ptr(out), _ptr(offs), cap), "az_game_stars_rect")
+    return out[:V], offs
 
 
 def typed_q(tag, x):
@@ -222,6 +244,11 @@ class Engine:
         """-> number of leaves; boards in self.leaf_boards[:k], slots in self.leaf_slots[:k]."""
         return _check(lib().az_mcts_collect(self.h, self._pb, self._ps, self.slots,
                                             int(threads)), "az_mcts_collect")
+
+    def leaf_stars(self, k, threads=1):
+        """The stars of the last collect's k leaves (game_stars on leaf_boards[:k]) -> (rows, offs)
+        for predict_both_stars; a pure function of the boards, the search is untouched."""
+        return game_stars(self.kind, self.shape, self.leaf_boards[:k], threads)
 
     def feed(self, k, pi=None, v=None, gpi=None, gv=None, failed=False):
         """Network outputs for the last collect's k leaves (or failed=True: the reference's

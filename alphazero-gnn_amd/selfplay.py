@@ -24,6 +24,15 @@ batch-1 vs batch-B CPU GEMMs are not.  A UCB near-tie can ther
 differently for different G or rank counts; tests/test_gpu_selfplay.py measures the action
 agreement and locates the first divergence.
 
+Leaves with neighbours (args.gnn_neighbors with args.gnn_neighbors_lockstep): every request of a
+round goes out as a star -- the board followed by MCTS.leaf_children(board), built by
+az_game_stars_rect in the engine lanes and by MCTS.leaf_children in the Python driver -- and the
+round is ONE nnet.predict_both_stars(rows, offs) call (an expand_tree root predict ignores its GNN
+row).  A plugin network without predict_both_stars is served per leaf with predict and
+predict_with_gnn(board, neighbor_states=children).  The contract above holds per star: given the
+same network outputs per (leaf, children), an episode is the one the sequential
+Coach.executeEpisode plays with gnn_neighbors, for every G, lane count and rank count.
+
 Network failures follow the reference (uniform priors, value 0 per leaf, MCTS.py:195-200) and
 are counted in nn_fallback; an expand_tree root predict that fails propagates (MCTS.py:108-113).
 """
@@ -37,15 +46,50 @@ from Coach import episode_g
 from MCTS import MCTS
 
 
+def lockstep_stars(args):
+    """True when the lock-step drivers evaluate every leaf with its children (use_gnn,
+    gnn_neighbors and the opt-in gnn_neighbors_lockstep all set)."""
+    return bool(_args_val(args, "use_gnn", False)) and bool(_args_val(args, "gnn_neighbors", False)) \
+        and bool(_args_val(args, "gnn_neighbors_lockstep", False))
+
+
+def pack_stars(boards, children):
+    """boards and children(board) -> (rows int8 [V][cols][rows], offs int32 [B+1]): star b is the
+    board followed by its children, the layout of az_game_stars_rect."""
+    stars = [[np.asarray(b)] + [np.asarray(c) for c in children(b)] for b in boards]
+    offs = np.zeros(len(stars) + 1, np.int32)
+    offs[1:] = np.cumsum([len(s) for s in stars])
+    rows = np.stack([r for s in stars for r in s]).astype(np.int8)
+    return rows, offs
+
+
+def _stars_per_leaf(nnet, rows, offs, wants=None):
+    """The per-leaf route for a network without predict_both_stars: predict on the leaf and
+    predict_with_gnn(leaf, neighbor_states=children), as MCTS.evaluate_request calls them."""
+    n = len(offs) - 1
+    std = [nnet.predict(rows[offs[i]]) for i in range(n)]
+    gnn = [nnet.predict_with_gnn(rows[offs[i]],
+                                 neighbor_states=list(rows[offs[i] + 1:offs[i + 1]]))
+           if wants is None or wants[i] else std[i] for i in range(n)]
+    return (np.stack([p for p, _ in std]).astype(np.float32),
+            np.array([x for _, x in std], np.float32),
+            np.stack([p for p, _ in gnn]).astype(np.float32),
+            np.array([x for _, x in gnn], np.float32))
+
+
 class BatchEvaluator:
     """Serves a list of leaf requests [(board, want_gnn)] with one batched network call.
 
     Uses nnet.predict_both (one trunk pass, standard + GNN outputs) or nnet.predict_batch when
     the network has them; a plugin network without batch entry points is served row by row
-    with its batch-1 predict / predict_with_gnn, exactly like the sequential path."""
+    with its batch-1 predict / predict_with_gnn, exactly like the sequential path.
 
-    def __init__(self, nnet):
+    children (a callable board -> list of boards, MCTS.leaf_children): every request of a round
+    that wants the GNN goes out as a star in ONE nnet.predict_both_stars(rows, offs) call."""
+
+    def __init__(self, nnet, children=None):
         self.nnet = nnet
+        self.children = children
         self.calls = 0
         self.rows = 0
 
@@ -54,6 +98,8 @@ class BatchEvaluator:
         self.calls += 1
         self.rows += n
         want_gnn = any(w for _, w in requests)
+        if want_gnn and self.children is not None:
+            return self._stars(requests)
         fn = getattr(self.nnet, "predict_both" if want_gnn else "predict_batch", None)
         if fn is None:
             return [self._single(r) for r in requests]
@@ -69,6 +115,20 @@ class BatchEvaluator:
                     for i in range(n)]
         pi, v = out
         return [((pi[i], v[i]), None, None) for i in range(n)]
+
+    def _stars(self, requests):
+        n = len(requests)
+        try:
+            rows, offs = pack_stars([b for b, _ in requests], self.children)
+            fn = getattr(self.nnet, "predict_both_stars", None)
+            if fn is not None:
+                pi, v, gpi, gv = fn(rows, offs)
+            else:
+                pi, v, gpi, gv = _stars_per_leaf(self.nnet, rows, offs, [w for _, w in requests])
+        except Exception as e:  # a batch fails as a whole, as in __call__
+            return [(None, None, e)] * n
+        return [((pi[i], v[i]), (gpi[i], gv[i]) if requests[i][1] else None, None)
+                for i in range(n)]
 
     def _single(self, request):
         board, want_gnn = request
@@ -93,7 +153,8 @@ def play_episodes(game, nnet, args, episodes, seeds, parallel_games=64, evaluato
 
     seeds: {episode: RandomState seed}.  Returns {episode: (std_examples, gnn_examples)}, each
     exactly what Coach.executeEpisode returns for that episode."""
-    evaluator = evaluator or BatchEvaluator(nnet)
+    evaluator = evaluator or BatchEvaluator(
+        nnet, MCTS(game, nnet, args).leaf_children if lockstep_stars(args) else None)
     pending = list(episodes)[::-1]
     live = []              # [episode, generator, pending request]
     results = {}
@@ -128,9 +189,14 @@ def play_episodes(game, nnet, args, episodes, seeds, parallel_games=64, evaluato
     return results
 
 
-def _net_call(nnet, boards, want_gnn):
+def _net_call(nnet, boards, want_gnn, stars=None):
     """One batched network call -> (pi, v, gpi, gv) float32 arrays (gpi/gv None w/o GNN).
-    Falls back to per-board calls for a plugin network without batch entry points."""
+    Falls back to per-board calls for a plugin network without batch entry points.  stars =
+    (rows, offs) of the boards' stars: predict_both_stars (or its per-leaf fallback)."""
+    if want_gnn and stars is not None:
+        if hasattr(nnet, "predict_both_stars"):
+            return nnet.predict_both_stars(*stars)
+        return _stars_per_leaf(nnet, *stars)
     if want_gnn and hasattr(nnet, "predict_both"):
         return nnet.predict_both(boards)
     if not want_gnn and hasattr(nnet, "predict_batch"):
@@ -158,12 +224,16 @@ class _Immediate:
         return self.out
 
 
-def _launch(nnet, boards, want_gnn, stream=None):
-    fn = getattr(nnet, "predict_both_async" if want_gnn else "predict_batch_async", None)
+def _launch(nnet, boards, want_gnn, stream=None, stars=None):
+    stars = stars if want_gnn else None
+    name = "predict_batch_async" if not want_gnn else \
+        "predict_both_async" if stars is None else "predict_both_stars_async"
+    fn = getattr(nnet, name, None)
     try:
         if fn is not None:
-            return fn(boards) if stream is None else fn(boards, stream=stream)
-        return _Immediate(_net_call(nnet, boards, want_gnn))
+            a = (boards,) if stars is None else stars
+            return fn(*a) if stream is None else fn(*a, stream=stream)
+        return _Immediate(_net_call(nnet, boards, want_gnn, stars))
     except Exception as ex:
         return _Immediate(err=ex)
 
@@ -183,6 +253,8 @@ class _Lane:
         self.predicting = {}      # slot -> board waiting for a standard prediction
         self.k, self.pred = 0, []
         self.rounds = self.rows = 0
+        self.with_stars = lockstep_stars(args)
+        self.stars = None         # (rows, offs) of the last gather's boards
 
     def _handle(self, slot, req):
         if req[0] == "search":
@@ -234,6 +306,9 @@ class _Lane:
                                                        for _, b in self.pred])])
         self.rounds += 1
         self.rows += len(boards)
+        if self.with_stars:
+            from mcts_native import game_stars
+            self.stars = game_stars(self.eng.kind, self.eng.shape, boards, self.threads)
         return boards
 
     def deliver(self, pending):
@@ -308,7 +383,7 @@ def play_episodes_native(game, nnet, args, episodes, seeds, parallel_games=256, 
         if lane.live():
             boards = lane.gather()
             if boards is not None:
-                inflight[i] = _launch(nnet, boards, use_gnn)
+                inflight[i] = _launch(nnet, boards, use_gnn, stars=lane.stars)
                 idle = 0
             else:
                 lane.deliver(None)          # searches that finished without a leaf
@@ -347,6 +422,8 @@ class _EpisodeLane:
         self.collect_s = 0.0       # main-thread time inside the engine's (feed_)collect calls
         self.assembler, self.pending = None, []
         self.fed = None            # rows of the last batch, fed by the next gather
+        self.with_stars = lockstep_stars(args)
+        self.stars = None          # (rows, offs) of the last gather's leaves
 
     def start(self):
         while self.queue and self.free:
@@ -401,6 +478,8 @@ class _EpisodeLane:
             return None
         self.rounds += 1
         self.rows += self.k
+        if self.with_stars:
+            self.stars = self.eng.leaf_stars(self.k, thr)
         return self.eng.leaf_boards[:self.k]
 
     def deliver(self, pending):
@@ -460,7 +539,7 @@ def play_episodes_engine(game, nnet, args, episodes, seeds, parallel_games=1024,
             lane.assembler = pool
     for lane in L:
         lane.start()
-    streams = _lane_streams(nnet, use_gnn, lanes)
+    streams = _lane_streams(nnet, use_gnn, lanes, lockstep_stars(args))
     inflight = [None] * lanes
     # diagnostics (tools/sp_pipeline_probe.py): stats["timeline"] = [] asks for one record per
     # lock-step round -- host times and the batch's GPU span from timing events on its stream
@@ -517,7 +596,7 @@ def play_episodes_engine(game, nnet, args, episodes, seeds, parallel_games=1024,
                     if tl_on:
                         e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
                         e0.record(streams[i])
-                    inflight[i] = _launch(nnet, boards, use_gnn, streams[i])
+                    inflight[i] = _launch(nnet, boards, use_gnn, streams[i], stars=lane.stars)
                     if tl_on:
                         e1.record(streams[i])
                         gpu_ev.append((len(stats["timeline"]), e0, e1))
@@ -559,14 +638,15 @@ def play_episodes_engine(game, nnet, args, episodes, seeds, parallel_games=1024,
     return results
 
 
-def _lane_streams(nnet, use_gnn, lanes):
+def _lane_streams(nnet, use_gnn, lanes, stars=False):
     """One HIP stream per lane for nets whose batched predict takes one (wrappers.py: each
     stream has its own device scratch), so a lane's batch can start while the other lane's is
     still on the GPU; every stream first waits for the work already queued on the current
     stream (parameter updates).  [None] * lanes otherwise (everything on the current stream)."""
     import inspect
     import os
-    fn = getattr(nnet, "predict_both_async" if use_gnn else "predict_batch_async", None)
+    fn = getattr(nnet, "predict_batch_async" if not use_gnn else
+                 "predict_both_stars_async" if stars else "predict_both_async", None)
     if lanes < 2 or fn is None or "stream" not in inspect.signature(fn).parameters or \
             os.environ.get("AZ_SP_ONE_STREAM") == "1":
         return [None] * lanes

@@ -613,6 +613,35 @@ int az_gnn_star_infer(const float* x, int ldstar, const int* counts, int B, int 
                       const az_gnn_layer_w* layers, float* x0, void* ws, size_t ws_bytes,
                       void* stream);
 
+/* The same layer stack on ANY number of stars of any size, packed: the batched route of lock-step
+ * self-play with gnn_neighbors (hundreds of leaves per round), where the node update is dense
+ * matrix products rather than weight streaming.
+ *   x       [V][F], the packed feature rows of B stars; never written, never copied
+ *   offs    int [B+1] in HBM (or mapped host memory), ascending, offs[0] = 0, offs[B] = V: star b is
+ *           rows offs[b] .. offs[b+1]-1, its first row the leaf, the rest its neighbours in the
+ *           caller's order.  Any star size >= 1 (TicTacToe 3x3: up to 10 rows, 5x5: up to 26).
+ *   x0      [B][F]: row 0 of each star after L layers.  May not alias x.
+ * Semantics are az_gnn_star_infer's: weights sigmoid(attention(.)), divided by their sum only when
+ * the sum is > 0 (all 0: the aggregate is 0), summed and aggregated in neighbour order; a one-row
+ * star returns its row bit for bit at every L (L = 0 included).
+ * Per layer: attention.0 factored per node as ONE K-major product of the V rows with att_w1 read
+ * as [2H][F] (from layer 1 on a second B-row product for the updated row 0s); one kernel that forms
+ * the weights, their sum, the aggregate and the operand row TA[b] = [t | agg] ([B][2F]; HBM-bound:
+ * (n-1) F 4 bytes read and 2 F 4 bytes written per star); gate.0 and update_net.0 as two plain
+ * K-major GEMMs on TA (K = 2F); update_net.2 (K = F) with the gated-residual epilogue.  All
+ * products go through az_gemm_f32's dispatch, so which tile serves which B is its business: a
+ * row is within 1e-5 of az_gnn_star_infer's but NOT bit-identical to it, and may differ between
+ * values of B.  Two identical calls give equal bits (no atomics, fixed summation orders).
+ * B >= 1 (B == 0: nothing to do), V >= B, F % 16 == 0, H % 4 == 0, 0 <= L <= 4; x, x0, ws and the
+ * weight matrices 16-byte aligned.  A bad shape, a null or misaligned pointer or a short workspace
+ * returns AZ_EINVAL with a message before any launch; so does a non-ascending offs when offs is
+ * host memory (az_host_alloc / pinned) -- offs in HBM is clamped into the V rows by the kernels.
+ * ws >= az_gnn_star_batch_ws_bytes(B, V, F, H, L) (0 for a rejected shape). */
+size_t az_gnn_star_batch_ws_bytes(int B, int V, int F, int H, int L);
+int az_gnn_star_batch_infer(const float* x, const int* offs, int B, int V, int F, int H, int L,
+                            const az_gnn_layer_w* layers, float* x0, void* ws, size_t ws_bytes,
+                            void* stream);
+
 /* predict_with_gnn of a Connect4 leaf with its neighbourhood (Connect4GNN.py:86-120 on the star
  * [board] + neighbor_states: extract_features, PolicyValueGNN.forward, the heads of row 0) as ONE
  * host call with direct launches: the board's fused trunk (az_c4_trunk_fwd for 7x7,

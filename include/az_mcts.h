@@ -188,6 +188,15 @@ int az_game_next_canonical_rect(int game, int nx, int ny, const int8_t* board, i
  * ascending order, at most `cap`), written to out [cap][n*n]; returns their count (0 for a
  * terminal board).  The arena's speculative leaf batches use it (mcts_native.ArenaPlayer). */
 int az_game_children(int game, int n, const int8_t* board, int cap, int8_t* out);
+/* The stars of a batch of leaves for gnn_neighbors (MCTS.leaf_children): for each of `count`
+ * canonical non-terminal boards [nx][ny], the board itself, then the canonical next state of every
+ * valid action in ascending action order, TERMINAL CHILDREN INCLUDED (unlike az_game_children).
+ * Rows are packed into out [cap_rows][nx * ny]; star i is rows offs[i] .. offs[i+1]-1, offs
+ * [count+1] with offs[0] = 0.  Returns the row count, or AZM_EINVAL before anything is written
+ * when cap_rows is too small (count * (A + 1) always fits).  A pure function of each board, run on
+ * up to `threads` host threads. */
+int az_game_stars_rect(int game, int nx, int ny, const int8_t* boards, int count, int threads,
+                       int8_t* out, int32_t* offs, int cap_rows);
 /* np.sum of a float64 vector (NumPy's pairwise summation), for tests. */
 double az_np_pairwise_sum(const double* a, int n);
 
