@@ -113,6 +113,10 @@ class Coach:
         if lockstep and not (_flag(args, "use_gnn") and _flag(args, "gnn_neighbors")):
             raise ValueError("gnn_neighbors_lockstep batches the star evaluation of gnn_neighbors: "
                              "it needs both use_gnn and gnn_neighbors")
+        if _flag(args, "gnn_neighbors_train") and not (_flag(args, "use_gnn")
+                                                       and _flag(args, "gnn_neighbors")):
+            raise ValueError("gnn_neighbors_train trains the GNN on the child stars gnn_neighbors "
+                             "evaluates: it needs both use_gnn and gnn_neighbors")
         if _flag(args, "gnn_neighbors") and not lockstep:
             # the leaf's neighbourhood is built by the Python search (MCTS.evaluate_request);
             # without gnn_neighbors_lockstep neither the native engine nor the lock-step drivers

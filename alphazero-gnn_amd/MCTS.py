@@ -25,6 +25,7 @@ import math
 import numpy as np
 
 import nn_fallback
+import stars
 
 EPS = 1e-8
 
@@ -62,10 +63,8 @@ class MCTS:
     def leaf_children(self, board):
         """The neighbourhood of a leaf for args.gnn_neighbors: the canonical next state of every
         valid action in action order, stepped the way search_g steps (terminal children
-        included)."""
-        valids = self.game.getValidMoves(board, 1)
-        return [self.game.getCanonicalForm(*self.game.getNextState(board, 1, a))
-                for a in range(self.game.getActionSize()) if valids[a]]
+        included): stars.children, which the training stars are built from too."""
+        return stars.children(self.game, board)
 
     # ------------------------------------------------------------------ batch-1 driver
     def evaluate_request(self, request):

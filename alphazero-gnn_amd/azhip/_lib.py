@@ -164,6 +164,14 @@ SIGNATURES = {
     "az_gnn_star_batch_infer": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(LayerW), c_void_p, c_void_p, c_size_t,
                                         c_void_p]),
+    "az_gnn_star_batch_save_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "az_gnn_star_batch_train_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "az_gnn_star_batch_fwd_train": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                            ctypes.POINTER(LayerW), c_void_p, c_void_p, c_size_t,
+                                            c_void_p, c_size_t, c_void_p]),
+    "az_gnn_star_batch_bwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                      ctypes.POINTER(LayerW), c_void_p, c_size_t, c_void_p,
+                                      ctypes.POINTER(LayerGrads), c_void_p, c_size_t, c_void_p]),
     "az_c4_star_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "az_c4_star_eval_fwd": (c_int, [ctypes.POINTER(C4StarEval), c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p]),

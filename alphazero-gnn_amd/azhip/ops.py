@@ -527,6 +527,68 @@ def gnn_star_batch_infer(x, offs, layers, out=None, ws=None, H=128, stream=None)
     return out, ws
 
 
+def gnn_star_batch_save_bytes(B, V, F, num_layers, H=128):
+    """az_gnn_star_batch_save_bytes (no GPU work)."""
+    return int(_lib.load().az_gnn_star_batch_save_bytes(B, V, F, H, num_layers))
+
+
+def gnn_star_batch_train_ws_bytes(B, V, F, num_layers, H=128):
+    """az_gnn_star_batch_train_ws_bytes (no GPU work)."""
+    return int(_lib.load().az_gnn_star_batch_train_ws_bytes(B, V, F, H, num_layers))
+
+
+def _star_train_args(what, x, offs, layers, H):
+    _need(x, name="x")
+    _need(offs, torch.int32, "offs")
+    V, F = x.shape
+    B = offs.numel() - 1
+    if not x.is_contiguous():
+        raise ValueError(f"{what}: x must be contiguous")
+    nl = len(layers)
+    L = _lib.lib()
+    nsave = int(L.az_gnn_star_batch_save_bytes(B, V, F, H, nl)) if B > 0 else 0
+    nws = int(L.az_gnn_star_batch_train_ws_bytes(B, V, F, H, nl)) if B > 0 else 0
+    if B > 0 and nws == 0:
+        raise ValueError(f"{what}: unsupported shape B={B} V={V} F={F} H={H} L={nl}")
+    lw = (LayerW * max(nl, 1))(*[layer_weights(Wl) for Wl in layers])
+    return L, B, V, F, nl, nsave, nws, lw
+
+
+def gnn_star_batch_fwd_train(x, offs, layers, out=None, save=None, H=128):
+    """az_gnn_star_batch_fwd_train: gnn_star_batch_infer's arguments and result, keeping in `save`
+    (a uint8 tensor, allocated when None or short) what gnn_star_batch_bwd needs.  Returns
+    (out [B][F], save)."""
+    L, B, V, F, nl, nsave, nws, lw = _star_train_args("gnn_star_batch_fwd_train", x, offs, layers,
+                                                      H)
+    dev = _dev(x)
+    if save is None or save.numel() < nsave:
+        save = torch.empty((max(nsave, 256),), dtype=torch.uint8, device=dev)
+    ws = workspace(dev, max(nws, 256))
+    out = torch.empty((max(B, 0), F), device=dev) if out is None else out
+    _lib.check(L.az_gnn_star_batch_fwd_train(_p(x), _p(offs), B, V, F, H, nl, lw, _p(out),
+                                             _p(save), ctypes.c_size_t(save.numel()), _p(ws),
+                                             ctypes.c_size_t(ws.numel()), _stream()),
+               "az_gnn_star_batch_fwd_train")
+    return out, save
+
+
+def gnn_star_batch_bwd(x, offs, layers, save, dx0, grads, H=128):
+    """az_gnn_star_batch_bwd: from dx0 [B][F] = d loss / d (gnn_star_batch_fwd_train's out) and
+    that call's `save`, WRITES the gradient of every tensor of every layer into `grads` (a list of
+    dicts with GNNLayer state_dict suffixes, like `layers`)."""
+    L, B, V, F, nl, nsave, nws, lw = _star_train_args("gnn_star_batch_bwd", x, offs, layers, H)
+    _need(dx0, name="dx0")
+    if tuple(dx0.shape) != (B, F) or not dx0.is_contiguous() or len(grads) != nl:
+        raise ValueError("gnn_star_batch_bwd: dx0 must be a contiguous [B][F], one grads dict per "
+                         "layer")
+    lg = (LayerGrads * max(nl, 1))(*[layer_grads(Gl) for Gl in grads])
+    ws = workspace(_dev(x), max(nws, 256))
+    _lib.check(L.az_gnn_star_batch_bwd(_p(x), _p(offs), B, V, F, H, nl, lw, _p(save),
+                                       ctypes.c_size_t(save.numel()), _p(dx0), lg, _p(ws),
+                                       ctypes.c_size_t(ws.numel()), _stream()),
+               "az_gnn_star_batch_bwd")
+
+
 class C4StarEval:
     """az_c4_star_eval descriptor with its device scratch for up to max_B <= 8 stars of <= 9 boards
     of a cols x rows Connect4Net (`shape` with a fused trunk: star_shape_ok): W the net's parameter

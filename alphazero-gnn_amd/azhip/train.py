@@ -7,6 +7,10 @@ backward kernels + a fused Adam over the flat parameter buffer).
                writes .grad of the conv trunk / heads, but the next epoch's
                nnet_optimizer.zero_grad() (Connect4GNN.py:154) discards them unused, so that
                dead work is skipped.
+* gnn_star_step -- the GNN step with every sampled example on its own child star (the board, then
+               the canonical next state of every valid action), the graph args.gnn_neighbors
+               evaluates; behind args.gnn_neighbors_train, absent from the reference
+               (tests/test_gpu_star_train.py).
 
 Every step takes device tensors: boards int8 [B,cols,rows], target pi fp32 [B,A], target v fp32
 [B].  Any board shape runs; the gradients of both steps are checked against float64 autograd for
@@ -256,6 +260,74 @@ def gnn_grads(net, gnn, boards, tpi, tv, seed=0, drop_mask=None):
 def gnn_step(net, gnn, boards, tpi, tv, lr, seed=0, drop_mask=None):
     """One reference GNN training step (Connect4GNN.py:160-197) on the star over the batch."""
     loss = gnn_grads(net, gnn, boards, tpi, tv, seed, drop_mask)
+    adam_step(gnn, lr)
+    return loss
+
+
+# ------------------------------------------------------------------------------ child stars
+class GNNStarForward:
+    """extract_features of the V packed rows -> the layer stack per star (az_gnn_star_batch_
+    fwd_train: star b = rows offs[b] .. offs[b+1]-1, row 0 the example) -> output_transform and
+    the heads on the B row 0s, keeping activations.  Connect4's dropout mask is the counter RNG's
+    over the V * F feature elements."""
+
+    def __init__(self, net, gnn, rows, offs, seed=0, drop_mask=None):
+        self.net, self.gnn, self.offs = net, gnn, offs
+        if _kind(net) == "c4":
+            fw = C4Forward(net, rows, net.dropout, seed, drop_mask)
+        else:
+            fw = TTTForward(net, rows)
+        self.x = fw.s.contiguous()
+        self.layers = [layer.weights() for layer in gnn.layers]
+        self.x0, self.save = ops.gnn_star_batch_fwd_train(self.x, offs, self.layers)
+        Wg = gnn.params.views
+        self.y, self.hidden = ops.mlp2(self.x0, Wg["output_transform.0.weight"],
+                                       Wg["output_transform.0.bias"],
+                                       Wg["output_transform.2.weight"],
+                                       Wg["output_transform.2.bias"])
+        if _kind(net) == "c4":
+            self.logp, self.v, self.saved = c4_heads_fwd(net, self.y)
+        else:
+            self.logp, self.v, self.saved = ttt_heads_fwd(net, self.y)
+
+    def backward(self, dl, dv, GG):
+        net, gnn = self.net, self.gnn
+        if _kind(net) == "c4":
+            dy = c4_heads_bwd(net, self.y, dl, dv, self.saved, None)
+        else:
+            dy = ttt_heads_bwd(net, self.y, dl, dv, self.saved, None)
+        Wg = gnn.params.views
+        dx0 = ops.mlp2_bwd(self.x0, Wg["output_transform.0.weight"],
+                           Wg["output_transform.2.weight"], self.hidden, dy,
+                           {"w0": GG["output_transform.0.weight"],
+                            "b0": GG["output_transform.0.bias"],
+                            "w2": GG["output_transform.2.weight"],
+                            "b2": GG["output_transform.2.bias"]},
+                           want_dx=bool(gnn.layers))
+        grads = [{k[len(layer.prefix):]: g for k, g in GG.items() if k.startswith(layer.prefix)}
+                 for layer in gnn.layers]
+        if grads:
+            ops.gnn_star_batch_bwd(self.x, self.offs, self.layers, self.save, dx0, grads)
+
+
+def gnn_star_grads(net, gnn, rows, offs, tpi, tv, seed=0, drop_mask=None):
+    """The GNN step's loss on child stars and its gradient w.r.t. every PolicyValueGNN tensor
+    (written).  rows int8 [V,cols,rows] packs B stars, star b = rows offs[b] .. offs[b+1]-1 with
+    the example's board first and then the canonical next state of every valid action (stars.
+    pack_stars); offs int32 [B+1] on the device; tpi [B,A], tv [B].  The loss is the reference's
+    (Connect4GNN.py:187-193) on the B row 0s, B the number of stars.  Returns (l_pi, l_v)."""
+    GG = _grads(gnn)
+    B = offs.numel() - 1
+    fw = GNNStarForward(net, gnn, rows, offs, seed, drop_mask)
+    lrows = torch.empty((B, 2), device=rows.device)
+    dl, dv = ops.heads_loss_bwd(fw.logp, fw.v, tpi, tv, loss_rows=lrows)
+    fw.backward(dl, dv, GG)
+    return lrows.sum(0)
+
+
+def gnn_star_step(net, gnn, rows, offs, tpi, tv, lr, seed=0, drop_mask=None):
+    """One GNN training step in which every example aggregates its own children."""
+    loss = gnn_star_grads(net, gnn, rows, offs, tpi, tv, seed, drop_mask)
     adam_step(gnn, lr)
     return loss
 

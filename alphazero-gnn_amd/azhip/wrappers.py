@@ -765,6 +765,7 @@ class NetWrapper:
             raise ValueError(f"{type(self).__name__}: action size {A} > {self.MAX_ACTIONS} is "
                              f"not supported by the HIP heads kernels (board {game.getBoardSize()})")
         self.device = nets.default_device()
+        self.game = game          # the training stars of gnn_neighbors_train are built from it
         self.nnet = self.net_class(game, args, device=self.device)
         self.board_x, self.board_y = game.getBoardSize()
         self.action_size = game.getActionSize()
@@ -913,16 +914,28 @@ class NetWrapper:
                 _dev_array(pis, np.float32, self.device),
                 _dev_array(np.array(vs).astype(np.float64), np.float32, self.device))
 
-    def _gnn_batch(self, gnn_examples):
+    def _gnn_draw(self, gnn_examples):
         batch_idx = np.random.randint(0, len(gnn_examples),
                                       min(len(gnn_examples), self.args.batch_size))
         batch = [gnn_examples[i] for i in batch_idx]
         boards = [b for b, _, _, _, _, _, _ in batch]
         pis = [p for _, _, _, _, p, _, _ in batch]
         vs = [v for _, _, _, _, _, v, _ in batch]
-        return (_dev_array(boards, np.int8, self.device),
-                _dev_array(pis, np.float32, self.device),
+        return (boards, _dev_array(pis, np.float32, self.device),
                 _dev_array(np.array(vs).astype(np.float64), np.float32, self.device))
+
+    def _gnn_batch(self, gnn_examples):
+        boards, pis, vs = self._gnn_draw(gnn_examples)
+        return _dev_array(boards, np.int8, self.device), pis, vs
+
+    def _gnn_star_batch(self, gnn_examples):
+        """_gnn_batch's draw (the same np.random call) with every sampled board expanded into its
+        child star: (rows int8 [V,cols,rows], offs int32 [B+1], pis, vs) on the device."""
+        import stars
+        boards, pis, vs = self._gnn_draw(gnn_examples)
+        rows, offs = stars.board_stars(self.game, boards)
+        return (_dev_array(rows, np.int8, self.device),
+                torch.from_numpy(np.ascontiguousarray(offs, np.int32)).to(self.device), pis, vs)
 
     def _train(self, examples, gnn_examples=None):
         """Connect4GNN.py:122-197: fresh Adam per call, `epochs` x (CNN step on a batch sampled
@@ -949,7 +962,14 @@ class NetWrapper:
                     self._cnn_step_allreduce(b, p, v, lr)
                 else:
                     T.cnn_step(self.nnet, b, p, v, lr, seed=self.train_seed)
-            if self.has_gnn and gnn_examples and len(gnn_examples) > 0:
+            if (self.has_gnn and gnn_examples and len(gnn_examples) > 0
+                    and nets._args_get(self.args, "gnn_neighbors_train", False)):
+                # every example on its own child star; deterministic, so it runs whole on every
+                # rank in every train_parallel mode and the replicas stay equal
+                rows, offs, p, v = self._gnn_star_batch(gnn_examples)
+                self.train_seed += 1
+                T.gnn_star_step(self.nnet, self.gnn, rows, offs, p, v, lr, seed=self.train_seed)
+            elif self.has_gnn and gnn_examples and len(gnn_examples) > 0:
                 b, p, v = self._gnn_batch(gnn_examples)
                 self.train_seed += 1
                 if self._dp_world() > 1:

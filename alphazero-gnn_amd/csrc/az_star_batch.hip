@@ -16,28 +16,9 @@
 // Every GEMM goes through az::gemm_f32, so which tile serves which B is the dispatch's business:
 // rows are within 1e-5 of az_gnn_star_infer's but not bit-identical to them, and may differ
 // between values of B; two identical calls give equal bits (no atomics, fixed summation orders).
-#include "az_gemm.h"
+#include "az_star_batch.h"
 
 namespace az {
-
-constexpr int SB_TILE = 32;   // neighbour weights a block keeps in LDS at a time
-constexpr int SB_CH = 8;      // neighbour rows whose loads are in flight before the first add
-constexpr size_t SB_SPLIT_BYTES = size_t(40) << 20;   // split-K slabs of the layer GEMMs
-
-struct StarSpan {
-  int o, n;   // first row, rows
-};
-
-// offs[b] .. offs[b+1] clamped into the V rows (a bad value cannot index outside x), at least one
-// row, wave-uniform
-__device__ __forceinline__ StarSpan star_span(const int* __restrict__ offs, int b, int V) {
-  int o = offs[b];
-  const int e = offs[b + 1];
-  o = o < 0 ? 0 : (o > V - 1 ? V - 1 : o);
-  int n = e - o;
-  n = n < 1 ? 1 : (n > V - o ? V - o : n);
-  return {__builtin_amdgcn_readfirstlane(o), __builtin_amdgcn_readfirstlane(n)};
-}
 
 // TA[b] = [t_b | agg_b] for star blockIdx.y, columns blockIdx.x * 1024 ...; grid
 // (ceil(F / 1024), B), 256 threads.  t_b is t[b] (the row 0 the previous layer wrote) or, at
@@ -137,8 +118,6 @@ __global__ __launch_bounds__(256) void star_batch_row0_kernel(const float* __res
         *reinterpret_cast<const f32x4*>(x + (size_t)sp.o * F + k);
 }
 
-static size_t sb_pad(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
 struct StarBatchWs {
   size_t P, Pt, TA, gate, u1, tbuf, split, split_bytes, total;   // byte offsets
 };
@@ -160,11 +139,6 @@ static StarBatchWs star_batch_ws(int B, int V, int F, int H) {
                   (size_t(1) << 20);
   w.total = w.split + w.split_bytes;
   return w;
-}
-
-static bool star_batch_shape(int B, int V, int F, int H, int L) {
-  return B >= 0 && V >= B && F >= 16 && F % 16 == 0 && F <= (1 << 20) && H >= 4 && H % 4 == 0 &&
-         H <= (1 << 16) && L >= 0 && L <= AZ_STAR_MAX_LAYERS && (size_t)V * F < (size_t(1) << 40);
 }
 
 }  // namespace az

@@ -17,6 +17,9 @@ MI355X additions (absent from the reference; defaults reproduce its behaviour):
                              with their children in ONE batched star call (selfplay.py), so
                              --parallel_games > 1 and several ranks are allowed; config key
                              gnn_neighbors_lockstep
+    --gnn_neighbors_train    with --use_gnn --gnn_neighbors: the GNN step trains every sampled
+                             example on its own child star (azhip/train.py gnn_star_step) instead
+                             of the star over the batch; config key gnn_neighbors_train
     multi-GPU: python -m torch.distributed.run --nproc-per-node P --master-addr 127.0.0.1 main.py ...
                (one rank per GPU, backend nccl = RCCL; episodes sharded by index)
 """
@@ -147,6 +150,9 @@ def parse(argv=None):
     p.add_argument("--gnn_neighbors_lockstep", action="store_true", default=None,
                    help="with --use_gnn --gnn_neighbors: lock-step self-play with one batched star "
                         "evaluation per round (allows --parallel_games > 1 and several ranks)")
+    p.add_argument("--gnn_neighbors_train", action="store_true", default=None,
+                   help="with --use_gnn --gnn_neighbors: the GNN step trains every sampled example "
+                        "on its own child star")
     return p.parse_args(argv)
 
 
@@ -166,7 +172,7 @@ def build_args(a):
         sys.exit(1)
     args = config_to_args(config)
     for k in ("board_size", "board_rows", "numIters", "numMCTSSims", "parallel_games",
-              "train_parallel", "gnn_neighbors", "gnn_neighbors_lockstep"):
+              "train_parallel", "gnn_neighbors", "gnn_neighbors_lockstep", "gnn_neighbors_train"):
         if getattr(a, k) is not None:
             args[k] = getattr(a, k)
     args.use_gnn = a.use_gnn

@@ -734,6 +734,42 @@ int az_gnn_node_update_bwd(const float* x, const float* agg, int V, int F, int D
                            float* dagg, float* d_gate_w, float* d_gate_b, float* d_upd_w1,
                            float* d_upd_b1, float* d_upd_w2, float* d_upd_b2, void* ws,
                            size_t ws_bytes, void* stream);
+/* Training on child stars: az_gnn_star_batch_infer's layer stack on packed stars keeping what the
+ * backward needs, and that backward.  x [V][F], offs [B+1], layers and x0 [B][F] are
+ * az_gnn_star_batch_infer's, with the same semantics (weights sigmoid(attention(.)), divided by
+ * their sum only when it is > 0, summed and aggregated in neighbour order; a one-row star returns
+ * its row bit for bit).  The rows are float64-accurate like that call's but not its bits.
+ *   save   per layer (az_gnn_star_batch_save_bytes in all): P [V][2H] = x W1'^T (W1 read as
+ *          [2H][F]: [v][2q] target half, [v][2q+1] source half); Pt [B][2H], the same of the
+ *          updated row 0s (written from layer 1 on); TA = [t | agg] [B][2F]; gate, u1, u [B][F];
+ *          the raw weights a [V] (0 at a star's first row) and their sums s [B]
+ *   ws     az_gnn_star_batch_train_ws_bytes, one size for both calls; nothing in it is carried
+ *          from the forward to the backward
+ * az_gnn_star_batch_bwd takes dx0 [B][F] = d loss / d x0 and WRITES every tensor of grads[0..L).
+ * Only row 0 of a star changes in a layer and x is an input here (the trunk is frozen in the GNN
+ * step), so no gradient with respect to x is formed: between layers only dt [B][F] flows.  Per
+ * layer, last first: the gated residual (du = dt g, dg = dt u g (1 - g), both 0 for a one-row
+ * star, whose dt passes through); update_net.2, update_net.0 and gate.0 as transposed products
+ * over the B rows with az_colsum biases; d[t | agg] = du1 Wu1 + dg Wg, its first half added into
+ * dt, its second half dagg; one kernel per star (the F-long dots dagg . x_j, (n-1) F 4 bytes per
+ * star, the normalisation and sigmoid backward, the hidden-unit gradients into dP [V][2H] and, from
+ * layer 1 on, the target half into dPt [B][2H], per-star partials of attention.2 and
+ * attention.0.bias); d attention.0.weight = dP^T x (+ dPt^T t from layer 1 on); dt += dPt W1'.
+ * A batch of one-row stars writes zeros; a two-row star adds exactly zero to attention.*.
+ * No atomics, fixed orders: two identical calls give equal bits.
+ * Shapes and alignment as az_gnn_star_batch_infer, and H <= 1024; dx0 16-byte aligned, every
+ * gradient pointer non-null, the matrices 16-byte aligned.  A bad shape, a null or misaligned
+ * pointer, a short save or ws, or a non-ascending host offs returns AZ_EINVAL with a message
+ * before any launch.  B == 0 returns AZ_OK. */
+size_t az_gnn_star_batch_save_bytes(int B, int V, int F, int H, int L);
+size_t az_gnn_star_batch_train_ws_bytes(int B, int V, int F, int H, int L);
+int az_gnn_star_batch_fwd_train(const float* x, const int* offs, int B, int V, int F, int H, int L,
+                                const az_gnn_layer_w* layers, float* x0, void* save,
+                                size_t save_bytes, void* ws, size_t ws_bytes, void* stream);
+int az_gnn_star_batch_bwd(const float* x, const int* offs, int B, int V, int F, int H, int L,
+                          const az_gnn_layer_w* layers, const void* save, size_t save_bytes,
+                          const float* dx0, const az_gnn_layer_grads* grads, void* ws,
+                          size_t ws_bytes, void* stream);
 /* output_transform backward (gnn_utils.py:101-105): dW2, db2, dW0, db0, dh (scratch [M][F])
  * and dx (nullable).  ws >= az_colsum_ws_bytes(M, F) (+ split-K room). */
 int az_mlp2_bwd(const float* x, int M, int F, const float* w0, const float* w2,
