@@ -107,6 +107,12 @@ class Coach:
     def __init__(self, game, nnet, args):
         self.game = game
         self.nnet = nnet
+        gnn = getattr(nnet, "gnn", None)
+        if gnn is not None and hasattr(gnn, "num_layers"):
+            # the depth the network was built with against the keys of this run, before any game
+            # is played (the wrapper checked its own args when it was built)
+            from azhip.wrappers import check_star_depth
+            check_star_depth("Coach", gnn.num_layers, args)
         self.pnet = self.nnet.__class__(self.game, args)   # the competitor (Coach.py:21)
         self.args = args
         lockstep = bool(_flag(args, "gnn_neighbors_lockstep"))

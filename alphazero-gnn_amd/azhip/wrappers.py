@@ -748,6 +748,17 @@ def _graphs_enabled():
     return os.environ.get("AZ_NO_GRAPH", "0") in ("", "0")
 
 
+def check_star_depth(who, num_layers, args):
+    """The packed-star kernels (az_gnn_star_batch_infer / _fwd_train / _bwd) take at most
+    ops.STAR_MAX_LAYERS layers, and the two keys that route self-play or training through them
+    have no other route: rejected up front, like the action size, instead of after a self-play
+    iteration (train()) or inside the first lock-step round."""
+    for key in ("gnn_neighbors_train", "gnn_neighbors_lockstep"):
+        if int(num_layers) > ops.STAR_MAX_LAYERS and nets._args_get(args, key, False):
+            raise ValueError(f"{who}: gnn_layers={int(num_layers)} > {ops.STAR_MAX_LAYERS}, the "
+                             f"most the packed-star kernels take, cannot be combined with {key}")
+
+
 class NetWrapper:
     """Common body; subclasses choose the board network class and whether a GNN exists."""
 
@@ -773,6 +784,7 @@ class NetWrapper:
         if self.has_gnn:
             self.feature_dim = self.nnet.feature_dim
             num_layers = nets._args_get(args, "gnn_layers", 2)
+            check_star_depth(type(self).__name__, num_layers, args)
             self.gnn = nets.PolicyValueGNN(self.feature_dim, num_layers, device=self.device)
         self.train_seed = 0
 

@@ -20,6 +20,8 @@ MI355X additions (absent from the reference; defaults reproduce its behaviour):
     --gnn_neighbors_train    with --use_gnn --gnn_neighbors: the GNN step trains every sampled
                              example on its own child star (azhip/train.py gnn_star_step) instead
                              of the star over the batch; config key gnn_neighbors_train
+                             (both star keys take --gnn_layers up to 4, the packed-star kernels'
+                             limit; a deeper network is rejected when the wrapper is built)
     multi-GPU: python -m torch.distributed.run --nproc-per-node P --master-addr 127.0.0.1 main.py ...
                (one rank per GPU, backend nccl = RCCL; episodes sharded by index)
 """

@@ -237,6 +237,29 @@ def test_star_batch_rejected_arguments():
     assert call(Bc=0) == 0
 
 
+@pytest.mark.parametrize("B", [9, 70])
+def test_star_batch_infer_four_layers(B):
+    """L = 4, the deepest stack az_gnn_star_batch_infer accepts (AZ_STAR_MAX_LAYERS), at F = 1024
+    on a four-layer net of its own: the fp32 MFMA tile (B = 9) and gemm_x3's 128x128 tile
+    (B = 70), three rows of NaN after x."""
+    from oracle.nets import gnn_layer_star
+    F = 1024
+    gnn = _gnn(F, 4)
+    assert len(gnn.layers) == 4
+    x, offs = _stars(F, 300)
+    offs = offs[:B + 1]
+    x = x[:offs[-1]]
+    G64 = _f64(gnn.params)
+    cur = [x[offs[b]:offs[b + 1]].astype(np.float64) for b in range(B)]
+    for l in range(4):
+        cur = [gnn_layer_star(c, G64, l) for c in cur]
+    got = _infer(gnn, x, offs, 4, pad_rows=3).cpu().numpy()
+    assert np.isfinite(got).all()
+    worst = assert_close(f"star_batch/F{F}/B{B}/L4", got, np.stack([c[0] for c in cur]), TOL)
+    print(f"star_batch F={F} B={B} V={offs[-1]} L=4: max err {worst:.3g} "
+          f"({TOL / max(worst, 1e-300):.1f}x)")
+
+
 # ------------------------------------------------------------------------------ the wrappers
 def _wrapper(kind, shape, seed=0, **extra):
     _GNN.clear()

@@ -93,6 +93,19 @@ def test_star_infer_matches_float64(F):
         print(f"star_infer F={F} B={hi - lo} L={L}: max err {worst:.3g} ({TOL / max(worst, 1e-300):.1f}x)")
 
 
+def test_star_infer_four_layers():
+    """L = 4, the deepest stack az_gnn_star_infer accepts (AZ_STAR_MAX_LAYERS), at F = 1024 on a
+    four-layer net of its own: all eight stars of COUNTS in one call."""
+    F = 1024
+    gnn, x = _gnn(F, 4), _features(F)
+    assert len(gnn.layers) == 4
+    ref = _oracle_rows(_f64(gnn.params), x, COUNTS, 4)[4]
+    got = _infer(gnn, x, COUNTS, 4).cpu().numpy()
+    assert np.isfinite(got).all()
+    worst = assert_close(f"star_infer/F{F}/B8/L4", got, np.stack(ref), TOL)
+    print(f"star_infer F={F} B=8 L=4: max err {worst:.3g} ({TOL / max(worst, 1e-300):.1f}x)")
+
+
 def test_star_infer_quirks():
     """A one-row star returns its feature row (torch.equal, also with L = 0); attention.2.bias =
     -1e4 underflows every weight to 0, so the aggregate is 0 and not divided (gnn_utils.py:58-59);
@@ -293,6 +306,41 @@ def test_star_eval_matches_float64_from_device_and_host_buffers(shape):
             assert_close(f"{tag}/routes/{name}", got, one, 2 * TOL)
 
 
+@pytest.mark.parametrize("shape", [(4, 4), (7, 6)])
+@pytest.mark.parametrize("L", [0, 1, 3, 4])
+def test_star_eval_at_other_depths(shape, L):
+    """az_c4_star_eval_fwd with no layer (row 0 goes straight into output_transform), one, three
+    and four (AZ_STAR_MAX_LAYERS) layers on the square and the rectangular trunk: stars of 8, 1
+    and 5 boards, one evaluator per (shape, L), pi, log pi and v against float64."""
+    from azhip import nets, ops
+    torch.manual_seed(8600 + 100 * shape[0] + 10 * shape[1] + L)
+    nnet = nets.Connect4Net(_game(shape), {"dropout": 0.0}).eval()
+    gnn = nets.PolicyValueGNN(nnet.feature_dim, L).eval()
+    assert len(gnn.layers) == L
+    dev = nnet.params.device
+    A, B = shape[0] + 1, len(STAR_COUNTS)
+    boards = _star_boards(shape, STAR_COUNTS, 57 * shape[0] + shape[1] + L)
+    lists = [boards[b, :n] for b, n in enumerate(STAR_COUNTS)]
+    rpi, rlogp, rv = _float64_star_eval(lists, nnet.params, gnn.params, L)
+    nnet.params.sync()
+    gnn.params.sync()
+    ev = ops.C4StarEval(nnet.params, gnn.params, shape, A, L, 8, dev)
+    for t in (ev.feat, ev.x0, ev.hidden, ev.glogp):
+        t.fill_(float("nan"))
+    gpi = torch.full((8, A), float("nan"), device=dev)
+    gv = torch.full((8,), float("nan"), device=dev)
+    ops.c4_star_eval(ev, torch.from_numpy(boards).to(dev),
+                     torch.tensor(STAR_COUNTS, dtype=torch.int32, device=dev), B, gpi=gpi, gv=gv)
+    torch.cuda.synchronize()
+    pi, v = gpi.cpu().numpy(), gv.cpu().numpy()
+    assert np.isnan(pi[B:]).all() and np.isnan(v[B:]).all()
+    tag = f"star_eval/{shape[0]}x{shape[1]}/L{L}"
+    for name, got, ref in (("pi", pi[:B], rpi), ("logp", ev.glogp[:B].cpu().numpy(), rlogp),
+                           ("v", v[:B], rv)):
+        worst = assert_close(f"{tag}/{name}", got, ref, TOL)
+        print(f"{tag} {name}: max err {worst:.3g} ({TOL / max(worst, 1e-300):.1f}x)")
+
+
 # ------------------------------------------------------------------------------ the wrappers
 def _wrapper(shape, layers=2, seed=0):
     from connect4.Connect4GNN import Connect4GNNWrapper
@@ -364,6 +412,24 @@ def test_wrapper_routes_and_star_batches(monkeypatch):
         with monkeypatch.context() as m:
             m.setenv(var, val)
             check(f"{var}", stars[:2], [0, 1], "composition")
+
+
+def test_five_layers_take_the_composition():
+    """gnn_layers = 5 is beyond every star kernel (ops.STAR_MAX_LAYERS = 4): predict_star_batch on
+    a 4x4 wrapper takes the composition on the generic graph calls, within 1e-5 of float64."""
+    from azhip import ops
+    shape = (4, 4)
+    w = _wrapper(shape, layers=5)
+    assert w.gnn.num_layers == 5 > ops.STAR_MAX_LAYERS
+    rng = np.random.default_rng(11)
+    stars = [[b for b in rng.integers(-1, 2, size=(n,) + shape)] for n in (5, 1, 3)]
+    pi, v = w.predict_star_batch(stars)
+    assert w.star_route == "composition"
+    rpi, _, rv = _float64_star_eval(stars, w.nnet.params, w.gnn.params, 5)
+    assert pi.shape == (3, 5) and v.shape == (3,)
+    worst = assert_close("star_eval/wrapper/L5/pi", pi, rpi, TOL)
+    worst_v = assert_close("star_eval/wrapper/L5/v", v, rv, TOL)
+    print(f"star_eval wrapper L=5: pi max err {worst:.3g}, v max err {worst_v:.3g}")
 
 
 def test_tictactoe_star_takes_the_composition():

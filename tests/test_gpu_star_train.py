@@ -17,7 +17,12 @@ dx0 random normal, loss = sum(dx0 * x0).  Star sizes per case:
   split      1..6 cycled over 70       M > 64: the fp16-split GEMM form at K = 2F
   ones       [1, 1, 1, 1]              every layer gradient exactly zero, x0 = row 0 bit for bit
   pairs      [2, 2, 2]                 attention.* exactly zero
-  onelayer   [1, 2, 5], L = 1          Pt is never used"""
+  onelayer   [1, 2, 5], L = 1          Pt is never used
+  deep3      [1, 2, 5, 9, 34], L = 3   a middle layer: neither first nor last, so the forward reads
+                                       and writes the row-0 buffer and the backward adds into a dt
+                                       that already carries the layer above's accumulations
+  deep4      [3, 1, 2, 10], L = 4      the deepest stack the kernels accept
+and with L = 0 the forward returns the row 0s and the backward has nothing to write."""
 import itertools
 
 import numpy as np
@@ -40,8 +45,11 @@ CASES = {
     "ones": ([1, 1, 1, 1], 2),
     "pairs": ([2, 2, 2], 2),
     "onelayer": ([1, 2, 5], 1),
+    "deep3": ([1, 2, 5, 9, 34], 3),
+    "deep4": ([3, 1, 2, 10], 4),
 }
 SEEDS = {name: 8100 + i for i, name in enumerate(CASES)}
+SEEDS["deep3"], SEEDS["deep4"] = 8300, 8301
 # float64 autograd cancels d(a / a) exactly only where the roundings of its two terms agree; they
 # do for all six weights of this seed's stars (test_references_are_not_vacuous holds it to that)
 SEEDS["pairs"] = 8202
@@ -144,10 +152,13 @@ def run_kernels(name, nan_fill=False):
 
 
 @gpu
-@pytest.mark.parametrize("name", ["gemv", "mixed", "past8", "tile", "split", "pairs", "onelayer"])
+@pytest.mark.parametrize("name", ["gemv", "mixed", "past8", "tile", "split", "pairs", "onelayer",
+                                  "deep3", "deep4"])
 def test_star_train_kernels_match_float64(name):
-    """x0 and all 10 L layer tensors.  `mixed` runs twice, the second time into gradient buffers
-    full of NaN: equal bits (no atomics, fixed orders) and every element written."""
+    """x0 and all 10 L layer tensors.  `mixed` and `deep3` run twice, the second time into gradient
+    buffers full of NaN: equal bits (no atomics, fixed orders) and every element written.  The
+    one-row star of `deep3` passes through its middle layer untouched: x0[b] is row 0 bit for
+    bit."""
     (x0_64, g64), (x0_32, g32), S = kernel_reference(name)
     guard_reference(f"star_train/{name}", g64, S, all_zero=ALL_ZERO.get(name, ()))
     x0, got = run_kernels(name)
@@ -163,7 +174,7 @@ def test_star_train_kernels_match_float64(name):
             assert not got[k].numpy().any(), (name, k)
             continue
         check_grad(f"star_train/{name}/{k}", got[k].numpy(), g64[k], g32[k], S[k])
-    if name == "mixed":
+    if name in ("mixed", "deep3"):
         x0b, gotb = run_kernels(name, nan_fill=True)
         assert torch.equal(x0, x0b)
         for k in got:
@@ -182,6 +193,41 @@ def test_one_row_stars_write_zeros():
         assert torch.equal(g, torch.zeros_like(g)), k
 
 
+@gpu
+def test_no_layers_returns_row_zero_and_writes_nothing():
+    """L = 0: gnn_star_batch_fwd_train gives every star's row 0 bit for bit (x untouched), and
+    gnn_star_batch_bwd returns success with nothing to write: x, dx0 and the save buffer keep
+    their bits."""
+    from azhip import _lib, ops
+    sizes = [1, 2, 5, 9]
+    offs, _, _ = forest(sizes)
+    rng = np.random.default_rng(8400)
+    x = rng.standard_normal((int(offs[-1]), F)).astype(np.float32)
+    xd, od = cu(x), cu(offs)
+    x0, save = ops.gnn_star_batch_fwd_train(xd, od, [])
+    torch.cuda.synchronize()
+    assert tuple(x0.shape) == (len(sizes), F)
+    assert np.array_equal(x0.cpu().numpy(), x[offs[:-1]])
+    assert np.array_equal(xd.cpu().numpy(), x)
+    dx0 = cu(rng.standard_normal((len(sizes), F)).astype(np.float32))
+    keep_dx0 = dx0.clone()
+    save.fill_(171)
+    keep_save = save.clone()
+    assert ops.gnn_star_batch_bwd(xd, od, [], save, dx0, []) is None      # _lib.check passed: rc 0
+    torch.cuda.synchronize()
+    assert torch.equal(dx0, keep_dx0) and torch.equal(save, keep_save)
+    assert np.array_equal(xd.cpu().numpy(), x)
+    # the entry point itself, with null layers / save / workspace / gradients: 0, no launch
+    import ctypes
+    P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    rc = _lib.lib().az_gnn_star_batch_bwd(P(xd), P(od), len(sizes), int(offs[-1]), F, H, 0, None,
+                                          None, ctypes.c_size_t(0), P(dx0), None, None,
+                                          ctypes.c_size_t(0), None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert torch.equal(dx0, keep_dx0)
+
+
 # ------------------------------------------------------------------------------ whole step
 def _play(game, moves):
     b, p = game.getInitBoard(), 1
@@ -190,8 +236,8 @@ def _play(game, moves):
     return game.getCanonicalForm(b, p)
 
 
-def step_case(kind):
-    """(game, boards, net weights W, GNN weights G, dropout, feature function name)."""
+def step_case(kind, L=2):
+    """(game, boards, net weights W, GNN weights G of L layers, dropout)."""
     from azhip.weights import (connect4_net_spec, gnn_spec, synthetic_state_dict,
                                tictactoe_net_spec)
     if kind == "c4_4x4":
@@ -203,23 +249,23 @@ def step_case(kind):
         assert game.getValidMoves(boards[1], 1)[2] == 0
         assert game.getGameEnded(boards[2], 1) != 0
         W = synthetic_state_dict(connect4_net_spec(4, 5), 611)
-        return game, boards, W, synthetic_state_dict(gnn_spec(1024, 2), 612), P_DROP
+        return game, boards, W, synthetic_state_dict(gnn_spec(1024, L), 612), P_DROP
     if kind == "c4_7x6":
         from connect4.Connect4Game import Connect4Game
         game = Connect4Game(7, rows=6)
         boards = [_play(game, (3, 3, 4)), _play(game, (2, 2, 2, 2, 2, 2, 0, 4, 4)),
                   _play(game, (0, 6, 0, 6, 0, 5))]
         W = synthetic_state_dict(connect4_net_spec((7, 6), 8), 621)
-        return game, boards, W, synthetic_state_dict(gnn_spec(2688, 2), 622), P_DROP
+        return game, boards, W, synthetic_state_dict(gnn_spec(2688, L), 622), P_DROP
     from tictactoe.TicTacToeGame import TicTacToeGame
     game = TicTacToeGame(3)
     boards = [_play(game, ()), _play(game, (4,)), _play(game, (0, 4, 8, 2)),
               _play(game, (0, 1, 2, 4, 3, 5, 7, 6))]
     W = synthetic_state_dict(tictactoe_net_spec(3, 10), 631)
-    return game, boards, W, synthetic_state_dict(gnn_spec(128, 2), 632), 0.0
+    return game, boards, W, synthetic_state_dict(gnn_spec(128, L), 632), 0.0
 
 
-def step_nets(kind, game, W, G, dropout):
+def step_nets(kind, game, W, G, dropout, L=2):
     from types import SimpleNamespace
     from azhip import nets
     g = SimpleNamespace(getBoardSize=lambda: tuple(game.getBoardSize()),
@@ -228,10 +274,10 @@ def step_nets(kind, game, W, G, dropout):
         net = nets.Connect4Net(g, {"dropout": dropout}, init=W)
     else:
         net = nets.TicTacToeNet(g, {}, init=W)
-    return net, nets.PolicyValueGNN(net.feature_dim, 2, init=G)
+    return net, nets.PolicyValueGNN(net.feature_dim, L, init=G)
 
 
-def step_loss(kind, W, rows, offs, rowptr, col, tpi, tv, m, parts=False):
+def step_loss(kind, W, rows, offs, rowptr, col, tpi, tv, m, parts=False, L=2):
     """The GNN step's loss on child stars as a function of the GNN's parameters: the frozen CNN's
     (dropped) features of all V rows, the layers per star, output_transform and the CNN's heads
     on the row 0s, the reference's loss over the B stars."""
@@ -244,7 +290,7 @@ def step_loss(kind, W, rows, offs, rowptr, col, tpi, tv, m, parts=False):
         Wn = {k: v.to(next(iter(PG.values())).dtype) for k, v in Pn.items()}
         feats = (c4_features_rect(rows, Wn, m, P_DROP) if kind.startswith("c4")
                  else R.ttt_features(rows, Wn))
-        y = R.policy_value_gnn(feats, PG, 2, rowptr, col)[starts]
+        y = R.policy_value_gnn(feats, PG, L, rowptr, col)[starts]
         logp, v = (R.c4_heads if kind.startswith("c4") else R.ttt_heads)(y, Wn)
         if parts:
             B = len(tpi)
@@ -261,11 +307,24 @@ def test_gnn_star_grads_on_real_boards(kind):
     with a full column and one terminal (a one-row star), dropout 0.3 under an explicit mask over
     the V * F feature elements, read back for the reference; Connect4 7x6: three leaves;
     TicTacToe 3x3: four leaves, the empty board's star has 10 rows."""
+    _check_star_step(kind, 2)
+
+
+@gpu
+@pytest.mark.parametrize("L", [0, 3])
+def test_gnn_star_grads_at_other_depths(L):
+    """The Connect4 4x4 case with gnn_layers 0 (only the four output_transform tensors exist: the
+    row 0s go straight into output_transform) and 3 (a middle layer inside the whole step): every
+    tensor and both loss terms."""
+    _check_star_step("c4_4x4", L)
+
+
+def _check_star_step(kind, L):
     import stars
     from azhip import ops, train as T
     from gradcheck import ref_grads
     from oracle import torch_ref as R
-    game, boards, W, G, dropout = step_case(kind)
+    game, boards, W, G, dropout = step_case(kind, L)
     rows, offs = stars.board_stars(game, boards)
     sizes = np.diff(offs)
     if kind == "c4_4x4":
@@ -273,7 +332,7 @@ def test_gnn_star_grads_on_real_boards(kind):
     if kind == "ttt_3x3":
         assert sizes.max() == 10
     B, V, A = len(boards), len(rows), game.getActionSize()
-    net, gnn = step_nets(kind, game, W, G, dropout)
+    net, gnn = step_nets(kind, game, W, G, dropout, L)
     Fd = net.feature_dim
     tpi, tv = targets(B, A, 900 + V)
     mask = ops.dropout_mask(V * Fd, dropout, 7000 + V, "cuda") if dropout > 0 else None
@@ -282,15 +341,15 @@ def test_gnn_star_grads_on_real_boards(kind):
     got = {k: v.cpu().numpy() for k, v in gnn.params.grads.items()}
     m = mask.cpu().numpy().reshape(V, Fd) if mask is not None else None
     _, rowptr, col = forest(sizes.tolist())
-    run = step_loss(kind, W, rows, offs, rowptr, col, tpi, tv, m)
+    run = step_loss(kind, W, rows, offs, rowptr, col, tpi, tv, m, L=L)
     g64, g32 = ref_grads(run, G, torch.float64), ref_grads(run, G, torch.float32)
     S = abs_contributions(run, R.params(G, torch.float64))
-    assert set(g64) == set(G) and len(g64) == 24
-    name = f"star_step/{kind}"
+    assert set(g64) == set(G) == set(got) and len(g64) == 10 * L + 4
+    name = f"star_step/{kind}" + ("" if L == 2 else f"/L{L}")
     guard_reference(name, g64, S)
     for k in g64:
         check_grad(f"{name}/{k}", got[k], g64[k], g32[k], S[k])
-    parts = step_loss(kind, W, rows, offs, rowptr, col, tpi, tv, m, parts=True)
+    parts = step_loss(kind, W, rows, offs, rowptr, col, tpi, tv, m, parts=True, L=L)
     with torch.no_grad():
         l64 = [float(t) for t in parts(R.params(G, torch.float64, requires_grad=False))]
         l32 = [float(t) for t in parts(R.params(G, torch.float32, requires_grad=False))]
@@ -301,12 +360,13 @@ def test_gnn_star_grads_on_real_boards(kind):
 
 
 # ------------------------------------------------------------------------------ wrapper
-def _wrapper(**kw):
+def _wrapper(gnn_layers=2, **kw):
     from types import SimpleNamespace
     from connect4.Connect4Game import Connect4Game
     from connect4.Connect4GNN import Connect4GNNWrapper
     game = Connect4Game(4)
-    args = SimpleNamespace(dropout=0.3, gnn_layers=2, lr=0.001, epochs=1, batch_size=4, **kw)
+    args = SimpleNamespace(dropout=0.3, gnn_layers=gnn_layers, lr=0.001, epochs=1, batch_size=4,
+                           **kw)
     torch.manual_seed(77)
     return game, Connect4GNNWrapper(game, args)
 
@@ -372,6 +432,27 @@ def test_wrapper_without_the_key_never_builds_stars(monkeypatch):
     assert not torch.equal(w.gnn.params.flat, before)
 
 
+@gpu
+@pytest.mark.parametrize("key", ["gnn_neighbors_train", "gnn_neighbors_lockstep"])
+def test_depth_above_the_star_limit_is_rejected_at_construction(key):
+    """gnn_layers above ops.STAR_MAX_LAYERS with a key that has no route but the packed-star
+    kernels: the wrapper, and a Coach handed a deeper wrapper, raise ValueError naming the limit
+    before any game is played -- not AZ_EINVAL inside train() after a self-play iteration.
+    Without the keys the same depth builds (predict_star_batch then composes)."""
+    import Coach as C
+    from azhip import ops
+    assert ops.STAR_MAX_LAYERS == 4
+    flags = dict(use_gnn=True, gnn_neighbors=True)
+    with pytest.raises(ValueError, match=rf"gnn_layers=5 > {ops.STAR_MAX_LAYERS}.*{key}"):
+        _wrapper(gnn_layers=5, **flags, **{key: True})
+    _wrapper(gnn_layers=4, **flags, **{key: True})             # the limit itself is accepted
+    game, deep = _wrapper(gnn_layers=5, **flags)
+    assert deep.gnn.num_layers == 5
+    args = dict(vars(deep.args), **{key: True})
+    with pytest.raises(ValueError, match=rf"gnn_layers=5 > {ops.STAR_MAX_LAYERS}.*{key}"):
+        C.Coach(game, deep, args)
+
+
 # ------------------------------------------------------------------------------ arguments
 @gpu
 def test_star_train_rejected_arguments():
@@ -412,12 +493,29 @@ def test_star_train_rejected_arguments():
         ho.numpy()[:] = offs
         return L.az_gnn_star_batch_bwd(P(x, xo), P(ho), B, V, F, H, Lc, lw, P(save), sz(ns),
                                        P(dx0), lg, P(ws), sz(nws), None)
-    for fn in (fwd, bwd):
-        for kw, msg in ((dict(ns=nsave - 1), b"save of"), (dict(xo=4), b"alignment"),
-                        (dict(offs=[0, 5, 5, 15, 20]), b"not ascending"),
-                        (dict(offs=[0, 5, 6, 15, 19]), b"offs[0]"), (dict(Lc=5), b"bad shape")):
-            assert fn(**kw) == -1, (fn.__name__, kw)
-            assert msg in L.az_last_error(), (kw, L.az_last_error())
+    failed = []
+
+    def run():
+        try:
+            for fn in (fwd, bwd):
+                for kw, msg in ((dict(ns=nsave - 1), b"save of"), (dict(xo=4), b"alignment"),
+                                (dict(offs=[0, 5, 5, 15, 20]), b"not ascending"),
+                                (dict(offs=[0, 5, 6, 15, 19]), b"offs[0]"),
+                                (dict(Lc=5), b"bad shape")):
+                    assert fn(**kw) == -1, (fn.__name__, kw)
+                    assert msg in L.az_last_error(), (kw, L.az_last_error())
+        except BaseException as ex:   # reported on the test's own thread
+            failed.append(ex)
+
+    # az_last_error is per thread: the rejected calls run on a thread of their own, so the main
+    # thread keeps the empty message tests/test_lib_abi.py expects when the whole suite runs in
+    # one process (as tests/test_gpu_star_batch.py does)
+    import threading
+    t = threading.Thread(target=run)
+    t.start()
+    t.join()
+    if failed:
+        raise failed[0]
     torch.cuda.synchronize()
     assert bool(torch.isnan(x0).all()) and bool(torch.isnan(gnn.params.grad_flat).all())
     assert fwd() == 0 and bwd() == 0

@@ -144,6 +144,30 @@ def test_coach_needs_use_gnn_and_gnn_neighbors():
     assert C.Coach(game, StubNet(game), Args(**base))
 
 
+def test_coach_rejects_a_depth_beyond_the_star_kernels():
+    """A network with more GNN layers than ops.STAR_MAX_LAYERS under gnn_neighbors_train or
+    gnn_neighbors_lockstep: ValueError naming the limit when the Coach is built, not AZ_EINVAL
+    inside train() after a self-play iteration.  The limit itself, and a deeper network without
+    the keys, are accepted."""
+    import Coach as C
+    from azhip import ops
+    from connect4.Connect4Game import Connect4Game
+    game = Connect4Game(4)
+    base = dict(numEps=1, numMCTSSims=2, cpuct=1.0, tempThreshold=3, expand_by=1, use_gnn=True,
+                gnn_neighbors=True)
+
+    def net(layers):
+        class Deep(StubNet):
+            gnn = SimpleNamespace(num_layers=layers)
+        return Deep(game)
+    assert ops.STAR_MAX_LAYERS == 4
+    for key in ("gnn_neighbors_train", "gnn_neighbors_lockstep"):
+        with pytest.raises(ValueError, match=rf"gnn_layers=5 > 4.*{key}"):
+            C.Coach(game, net(5), Args(**base, **{key: True}))
+        assert C.Coach(game, net(4), Args(**base, **{key: True}))
+    assert C.Coach(game, net(5), Args(**base))
+
+
 def test_frozenlake_rejects_the_key():
     """FrozenLake has no GNN version, so use_gnn is never set for it: the key raises."""
     import Coach as C
