@@ -123,6 +123,12 @@ class Coach:
                                                        and _flag(args, "gnn_neighbors")):
             raise ValueError("gnn_neighbors_train trains the GNN on the child stars gnn_neighbors "
                              "evaluates: it needs both use_gnn and gnn_neighbors")
+        if _flag(args, "batch_invariant") and _flag(args, "gnn_neighbors"):
+            # the packed-star kernels go through az_gemm_f32's dispatch, which picks its tile by
+            # the row count: there is no invariant form of them yet
+            raise ValueError("batch_invariant cannot be combined with gnn_neighbors (with or "
+                             "without gnn_neighbors_lockstep): the star evaluation is not "
+                             "batch-invariant")
         if _flag(args, "gnn_neighbors") and not lockstep:
             # the leaf's neighbourhood is built by the Python search (MCTS.evaluate_request);
             # without gnn_neighbors_lockstep neither the native engine nor the lock-step drivers

@@ -108,6 +108,20 @@ class TttEval(ctypes.Structure):
                  ("glogp", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t)])
 
 
+EXACT_MAX_SEGMENTS, EXACT_C4, EXACT_TTT = 16, 0, 1
+
+
+class EvalExact(ctypes.Structure):
+    """az_eval_exact (include/az_hip.h)."""
+    _fields_ = ([("game", c_int), ("nx", c_int), ("ny", c_int), ("A", c_int), ("F", c_int)] +
+                [(f"{l}_{k}", c_void_p) for l in ("conv1", "conv2", "conv3", "fc1", "fc2",
+                                                    "fc_policy", "fc_value", "ot0", "ot2")
+                 for k in "wb"] +
+                [("max_B", c_int), ("feat", c_void_p), ("h1", c_void_p), ("h2", c_void_p),
+                 ("hidden", c_void_p), ("y", c_void_p), ("logp", c_void_p), ("glogp", c_void_p),
+                 ("ws", c_void_p), ("ws_bytes", c_size_t)])
+
+
 FL_MAX_LAYERS = 4
 
 
@@ -180,6 +194,13 @@ SIGNATURES = {
     "az_ttt_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "az_ttt_eval_fwd": (c_int, [ctypes.POINTER(TttEval), c_void_p, c_int, c_void_p, c_void_p,
                                 c_void_p, c_void_p, c_void_p]),
+    "az_gemm_exact_plan": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "az_gemm_exact_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "az_gemm_exact_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                  c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "az_eval_exact_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "az_eval_exact_fwd": (c_int, [ctypes.POINTER(EvalExact), c_void_p, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p]),
     "az_fl_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "az_fl_eval_fwd": (c_int, [ctypes.POINTER(FlEval), c_void_p, c_void_p, c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p]),

@@ -453,6 +453,95 @@ def c4r_eval(ev, boards_i8, B, pi=None, v=None, gpi=None, gv=None, stream=None):
                                           _p(gpi), _p(gv), s), "az_c4r_eval_fwd")
 
 
+def gemm_exact_plan(N, K):
+    """az_gemm_exact_plan: the K cut of linear_exact for an [N][K] weight, a list of segment
+    lengths that sum to K.  A function of (N, K) only; no GPU work."""
+    n = ctypes.c_int(0)
+    seg = (ctypes.c_int * _lib.EXACT_MAX_SEGMENTS)()
+    _lib.check(_lib.load().az_gemm_exact_plan(int(N), int(K), ctypes.byref(n), seg),
+               "az_gemm_exact_plan")
+    return [int(seg[i]) for i in range(n.value)]
+
+
+def linear_exact(x, w, b=None, act=ACT_NONE, out=None, M=None, ws=None):
+    """out = act(x @ w.T + b) as az_gemm_exact_f32: every output a fixed fp32 fmaf chain over
+    gemm_exact_plan's segments, so row i is the same bits at any M and any position.  x: [>= M, K]
+    (row stride taken from the tensor), w: [N, K] nn.Linear layout."""
+    _need(x, name="x")
+    _need(w, name="w")
+    M = x.shape[0] if M is None else M
+    N, K = w.shape
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.float32)
+    L = _lib.lib()
+    nb = int(L.az_gemm_exact_ws_bytes(M, N, K))
+    if ws is None and nb:
+        ws = workspace(x.device, max(nb, 64 << 20))
+    _lib.check(L.az_gemm_exact_f32(_p(x), x.stride(0), _p(w), w.stride(0), _p(b), act, _p(out),
+                                   out.stride(0), M, N, K, _p(ws),
+                                   ctypes.c_size_t(ws.numel() if ws is not None else 0), _stream()),
+               "az_gemm_exact_f32")
+    return out
+
+
+def exact_board(w_net):
+    """(game, cols, rows) of az_eval_exact for a board network (nets.Connect4Net /
+    nets.TicTacToeNet), or None when the board has no fused trunk."""
+    from . import nets
+    if isinstance(w_net, nets.TicTacToeNet):
+        return (_lib.EXACT_TTT, w_net.n, w_net.n) if 3 <= w_net.n <= 5 else None
+    if isinstance(w_net, nets.Connect4Net):
+        s = (getattr(w_net, "board_x", w_net.n), getattr(w_net, "board_y", w_net.n))
+        if s == (7, 7) or s in C4R_SHAPES or (s[0] == s[1] and s[0] in C4N_SIDES):
+            return (_lib.EXACT_C4,) + s
+    return None
+
+
+class EvalExact:
+    """az_eval_exact descriptor with its device scratch for up to max_B boards: W the board
+    network's parameter tensors, G the PolicyValueGNN's (None: no GNN tail), board = (game, cols,
+    rows) as exact_board returns it.  The tensors are read through the pointers taken here, so
+    they must be updated in place."""
+
+    def __init__(self, W, G, board, A, max_B, device):
+        game, nx, ny = board
+        ttt = game == _lib.EXACT_TTT
+        F = 128 * (nx - 2) * (ny - 2) if ttt else 64 * nx * ny
+        self.board, self.A, self.F, self.max_B = board, A, F, max_B
+        nb = int(_lib.lib().az_eval_exact_ws_bytes(max_B, game, nx, ny, A))
+        if nb == 0:
+            raise ValueError(f"az_eval_exact: unsupported shape game={game} cols={nx} rows={ny} "
+                             f"A={A} max_B={max_B}")
+        e = lambda *s: torch.empty(s, device=device, dtype=torch.float32)  # noqa: E731
+        self.feat = e(max_B, F)
+        self.h1 = e(max_B, 512) if ttt else None
+        self.h2 = e(max_B, 512) if ttt else None
+        self.hidden = e(max_B, F) if G is not None else None
+        self.y = e(max_B, F) if G is not None else None
+        self.logp, self.glogp = e(max_B, A), e(max_B, A)
+        self.ws = torch.empty((nb,), dtype=torch.uint8, device=device)
+        P = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        layers = ("conv1", "conv2", "conv3", "fc1", "fc2", "fc_policy", "fc_value")
+        have = set(W.keys())
+        wts = [P(W[f"{l}.{k}"]) if f"{l}.{k}" in have else None
+               for l in layers for k in ("weight", "bias")]
+        ot = [P(G[f"output_transform.{i}.{k}"]) if G is not None else None
+              for i in (0, 2) for k in ("weight", "bias")]
+        self.desc = _lib.EvalExact(game, nx, ny, A, F, *wts, *ot, max_B, P(self.feat), P(self.h1),
+                                   P(self.h2), P(self.hidden), P(self.y), P(self.logp),
+                                   P(self.glogp), P(self.ws), nb)
+        self._keep = (W, G)
+
+
+def eval_exact(ev, boards_i8, B, pi=None, v=None, gpi=None, gv=None, stream=None):
+    """az_eval_exact_fwd on `ev` (an EvalExact): the first B <= ev.max_B boards -> pi / v (standard
+    heads) and gpi / gv (GNN tail), each written when given; device tensors or HostBuffer views.
+    Queued on `stream` (default: the current stream); nothing is synchronised."""
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(_lib.lib().az_eval_exact_fwd(ctypes.byref(ev.desc), _p(boards_i8), B, _p(pi), _p(v),
+                                            _p(gpi), _p(gv), s), "az_eval_exact_fwd")
+
+
 STAR_MAX_NODES, STAR_MAX_STARS, STAR_MAX_LAYERS = (_lib.STAR_MAX_NODES, _lib.STAR_MAX_STARS,
                                                    _lib.STAR_MAX_LAYERS)
 

@@ -228,6 +228,89 @@ class _C4rDirectBatch(_DirectBatch):
         self.cap = cap
 
 
+class _ExactBatch(_DirectBatch):
+    """_DirectBatch under args.batch_invariant, for every board with a fused trunk (Connect4 and
+    TicTacToe, with or without a GNN): ONE az_eval_exact_fwd call per max_B rows, the same launch
+    sequence at 1 row and at 4,096, so a board's outputs do not depend on the batch it rides in.
+    Same host ring and ownership tokens; a batch above CAP rows runs as consecutive chunks on the
+    same scratch, which invariance makes the same result.  kind: "std" -> (pi, v, None, None),
+    "gnn" -> (None, None, gpi, gv), "both" -> all four."""
+
+    CAP = 4096
+
+    def __init__(self, w, stream=None):
+        super().__init__(w, stream)
+        self.fn = _lib.lib().az_eval_exact_fwd
+        self.fn_name = "az_eval_exact_fwd"
+
+    def _grow(self, n):
+        w = self.w
+        cap = min(self.CAP, max(1024, 1 << (int(n) - 1).bit_length()))
+        torch.cuda.synchronize(w.device)          # in-flight batches may use the old scratch
+        self.ev = ops.EvalExact(w.nnet.params, w.gnn.params if w.has_gnn else None,
+                                ops.exact_board(w.nnet), w.action_size, cap, w.device)
+        self.desc = self.ev.desc
+        self.cap = cap
+
+    def _entry(self, n):
+        """A host staging set of >= n rows no unread prediction holds (idle smaller ones go)."""
+        for e in self.ring:
+            if not e["busy"] and e["rows"] >= n:
+                return e
+        self.ring = [e for e in self.ring if e["busy"]]
+        w, A = self.w, self.w.action_size
+        rows = max(1024, 1 << (int(n) - 1).bit_length())
+        off = [0, (rows * w.board_x * w.board_y + 255) // 256 * 256]
+        for k in (A, 1, A, 1):
+            off.append(off[-1] + (4 * rows * k + 255) // 256 * 256)
+        hb = ops.HostBuffer(off[-1])
+        e = {"busy": False, "hb": hb, "rows": rows,
+             "in": hb.view(0, torch.int8, (rows, w.board_x, w.board_y)),
+             "out": [hb.view(off[1 + j], torch.float32, (rows, k) if k > 1 else (rows,))
+                     for j, k in enumerate((A, 1, A, 1))]}
+        self.ring.append(e)
+        return e
+
+    def launch(self, boards, both, kind=None):
+        kind = kind or ("both" if both else "std")
+        boards = np.asarray(boards)
+        n = boards.shape[0]
+        if n > self.cap and self.cap < self.CAP:
+            self._grow(n)
+        e = self._entry(n)
+        hin, outs = e["in"], e["out"]
+        hin.numpy()[:n] = boards.reshape(n, hin.shape[1], hin.shape[2])
+        pi, v = (outs[0], outs[1]) if kind != "gnn" else (None, None)
+        gpi, gv = (outs[2], outs[3]) if kind != "std" else (None, None)
+        s = self.stream if self.stream is not None else torch.cuda.current_stream(self.w.device)
+        P = lambda t, c0: None if t is None else ctypes.c_void_p(t[c0:].data_ptr())  # noqa: E731
+        for c0 in range(0, n, self.cap):
+            rc = self.fn(ctypes.byref(self.desc), P(hin, c0), min(self.cap, n - c0), P(pi, c0),
+                         P(v, c0), P(gpi, c0), P(gv, c0), ctypes.c_void_p(s.cuda_stream))
+            if rc:
+                _lib.check(rc, self.fn_name)
+        ev = torch.cuda.Event()
+        ev.record(s)
+        return _PendingDirect(e, (pi, v, gpi, gv), ev, n)
+
+
+class _ExactBatch1:
+    """What _graph1 hands out under args.batch_invariant: run() / run_rows() of the batch-1
+    evaluators on the exact route (a batch-1 call is then just a batch of one row)."""
+
+    def __init__(self, w, kind):
+        self.w, self.kind = w, kind
+
+    def run_rows(self, boards):
+        return self.w._exact(boards, self.kind).result()
+
+    def run(self, board):
+        """One board -> the packed row [pi, v(, gpi, gv)]."""
+        pi, v, gpi, gv = self.run_rows(np.asarray(board)[None])
+        parts = [a.reshape(-1) for a in (pi, v, gpi, gv) if a is not None]
+        return np.concatenate(parts).astype(np.float32, copy=False)
+
+
 class _PinnedRing:
     """Pinned host staging buffers reused round-robin (`depth` predictions in flight)."""
 
@@ -787,6 +870,12 @@ class NetWrapper:
             check_star_depth(type(self).__name__, num_layers, args)
             self.gnn = nets.PolicyValueGNN(self.feature_dim, num_layers, device=self.device)
         self.train_seed = 0
+        self.batch_invariant = bool(nets._args_get(args, "batch_invariant", False))
+        if self.batch_invariant and ops.exact_board(self.nnet) is None:
+            # rejected up front, like the action size: MCTS swallows a predict's error
+            raise ValueError(f"{type(self).__name__}: batch_invariant needs a board with a fused "
+                             f"trunk (Connect4 7x7, 4x4, 5x5, 6x6, 8x8, 7x6, 6x5, 5x4, 8x7; "
+                             f"TicTacToe 3x3 .. 5x5), not {game.getBoardSize()}")
 
     # -- evaluation ------------------------------------------------------------------------
     def _sync_params(self):
@@ -796,8 +885,24 @@ class NetWrapper:
         if self.has_gnn:
             self.gnn.params.sync()
 
+    def _exact(self, boards, kind, stream=None):
+        """args.batch_invariant: queue `boards` on the exact route (_ExactBatch, one per stream);
+        .result() -> (pi, v, gpi, gv), None where `kind` ("std", "gnn", "both") has none."""
+        self._sync_params()
+        self.nnet.eval()
+        if self.has_gnn:
+            self.gnn.eval()
+        directs = self.__dict__.setdefault("_exact_directs", {})
+        key = None if stream is None else stream.cuda_stream
+        d = directs.get(key)
+        if d is None:
+            d = directs[key] = _ExactBatch(self, stream)
+        return d.launch(boards, kind == "both", kind)
+
     def _graph1(self, kind):
         """The batch-1 graph of `kind`, captured on first use (None when disabled)."""
+        if self.batch_invariant:
+            return _ExactBatch1(self, kind)
         self._sync_params()
         if not _graphs_enabled():
             return None
@@ -833,6 +938,9 @@ class NetWrapper:
         (Connect4GNN.py:59-84; `neighbor_states` is accepted and unused as in
         Connect4Net.py:110)."""
         self.nnet.eval()
+        if self.batch_invariant:
+            pi, v, _, _ = self._exact(np.asarray(board)[None], "std").result()
+            return pi[0], v[0]
         g = self._graph1("std")
         if g is not None:
             out = g.run(board)
@@ -844,6 +952,9 @@ class NetWrapper:
     def predict_batch(self, boards):
         """Row-wise predict for [B,cols,rows] boards -> (pi float32[B,A], v float32[B])."""
         self.nnet.eval()
+        if self.batch_invariant and len(boards) > 0:
+            pi, v, _, _ = self._exact(boards, "std").result()
+            return pi, v
         if len(boards) == 1 and (g := self._graph1("std")) is not None:
             out = g.run(boards[0])
             return out[None, :-1], out[-1:]
@@ -855,6 +966,8 @@ class NetWrapper:
         stream: run it on that HIP stream with its own device scratch (the lock-step lanes give
         each lane a stream, so one lane's batch can overlap the other's on the GPU); the caller
         orders the stream after any parameter update (play_episodes_engine does)."""
+        if self.batch_invariant and len(boards) > 0:
+            return self._exact(boards, "both" if both else "std", stream)
         self._sync_params()
         if (self.has_gnn or _is_ttt(self) or _is_c4n(self) or _is_c4r(self)) \
                 and _direct_ok(self) \
@@ -1130,7 +1243,11 @@ class GNNWrapperMixin:
         (az_c4n_eval_fwd), the one for 7x6, 6x5, 5x4 and 8x7 boards (az_c4r_eval_fwd) and the
         TicTacToe one (az_ttt_eval_fwd, n = 3..5) compute every row of a batch of <= 8 with the
         batch-1 arithmetic (tests/test_gpu_selfplay.py, tests/test_gpu_c4n_eval.py,
-        tests/test_gpu_c4r_eval.py, tests/test_gpu_ttt_eval.py); 0 = no such guarantee."""
+        tests/test_gpu_c4r_eval.py, tests/test_gpu_ttt_eval.py); 0 = no such guarantee.  Under
+        args.batch_invariant every entry point is az_eval_exact_fwd, invariant at any batch size
+        (tests/test_gpu_exact.py): 1 << 30."""
+        if self.batch_invariant:
+            return 1 << 30
         return 8 if _direct_ok(self) else 0
 
     def predict(self, board):
@@ -1258,6 +1375,9 @@ class GNNWrapperMixin:
             return pi[0], v[0]
         self.nnet.eval()
         self.gnn.eval()
+        if self.batch_invariant:
+            _, _, gpi, gv = self._exact(np.asarray(board)[None], "gnn").result()
+            return gpi[0], gv[0]
         g = self._graph1("gnn")
         if g is not None:
             out = g.run(board)
@@ -1269,6 +1389,9 @@ class GNNWrapperMixin:
     def predict_batch_with_gnn(self, boards):
         self.nnet.eval()
         self.gnn.eval()
+        if self.batch_invariant and len(boards) > 0:
+            _, _, gpi, gv = self._exact(boards, "gnn").result()
+            return gpi, gv
         pi, v = self._eval(boards, True)
         return pi.cpu().numpy(), v.cpu().numpy()
 
@@ -1278,6 +1401,8 @@ class GNNWrapperMixin:
         self.nnet.eval()
         self.gnn.eval()
         A = self.action_size
+        if self.batch_invariant and len(boards) > 0:
+            return self._exact(boards, "both").result()
         g = self._graph1("both") if len(boards) <= 8 else None
         if isinstance(g, _Batch1Direct) and len(boards) > 0:
             return g.run_rows(np.asarray(boards))

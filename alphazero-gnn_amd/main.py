@@ -22,6 +22,11 @@ MI355X additions (absent from the reference; defaults reproduce its behaviour):
                              of the star over the batch; config key gnn_neighbors_train
                              (both star keys take --gnn_layers up to 4, the packed-star kernels'
                              limit; a deeper network is rejected when the wrapper is built)
+    --batch_invariant        a board's network outputs are the same bits whatever batch it rides in
+                             (exact-fp32 GEMMs, az_eval_exact_fwd): the seed fixes the run, not the
+                             seed together with --parallel_games and the rank count.  Slower than
+                             the default routes; not with --gnn_neighbors; config key
+                             batch_invariant
     multi-GPU: python -m torch.distributed.run --nproc-per-node P --master-addr 127.0.0.1 main.py ...
                (one rank per GPU, backend nccl = RCCL; episodes sharded by index)
 """
@@ -155,6 +160,9 @@ def parse(argv=None):
     p.add_argument("--gnn_neighbors_train", action="store_true", default=None,
                    help="with --use_gnn --gnn_neighbors: the GNN step trains every sampled example "
                         "on its own child star")
+    p.add_argument("--batch_invariant", action="store_true", default=None,
+                   help="evaluate every board with the same bits at any batch size (exact-fp32 "
+                        "GEMMs; slower; not with --gnn_neighbors)")
     return p.parse_args(argv)
 
 
@@ -174,7 +182,8 @@ def build_args(a):
         sys.exit(1)
     args = config_to_args(config)
     for k in ("board_size", "board_rows", "numIters", "numMCTSSims", "parallel_games",
-              "train_parallel", "gnn_neighbors", "gnn_neighbors_lockstep", "gnn_neighbors_train"):
+              "train_parallel", "gnn_neighbors", "gnn_neighbors_lockstep", "gnn_neighbors_train",
+              "batch_invariant"):
         if getattr(a, k) is not None:
             args[k] = getattr(a, k)
     args.use_gnn = a.use_gnn

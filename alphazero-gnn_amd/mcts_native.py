@@ -642,7 +642,9 @@ class ArenaPlayer:
         self.eng = Engine(game, 1, float(get("cpuct", 1.0)), self.use_gnn)
         self.mcts = NativeMCTS(self.eng, 0, game, args)
         rows = int(getattr(nnet, "batch_invariant_rows", 0) or 0) if prefetch else 0
-        self.spec = rows if rows >= 2 else 0
+        # 8 rows serve a leaf and its children; a net that is invariant at any batch size
+        # (batch_invariant: 1 << 30) gains nothing from a larger speculative buffer
+        self.spec = min(rows, 8) if rows >= 2 else 0
         self.calls = 0
         if self.spec:
             self._batch = np.zeros((self.spec,) + self.eng.shape, np.int8)

@@ -354,6 +354,76 @@ int az_ttt_eval_fwd(const az_ttt_eval* e, const int8_t* boards, int B, float* pi
                     float* gpi, float* gv, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Batch-invariant evaluation (config key batch_invariant): a board's outputs are the
+ * same bits whatever rides in the batch with it.  No reference counterpart: the reference evaluates
+ * one board per call, which is what these entry points make every batch size equal to.
+ *
+ * az_gemm_exact_f32: C = act(A W^T + bias), both operands K-major fp32 (the forward nn.Linear:
+ * A [M][K] row stride lda, W [N][K] row stride ldw, C [M][N] row stride ldc), fp32 accumulation on
+ * v_mfma_f32_32x32x2_f32.  The arithmetic is the contract:
+ *   - K is cut into S contiguous segments; S and the cut points are a function of (N, K) only,
+ *     reported by az_gemm_exact_plan (HOST function, no GPU work; seg_len receives S <=
+ *     AZ_EXACT_MAX_SEGMENTS lengths that sum to K);
+ *   - each segment is one chain acc = fmaf(a[k], w[k], acc) in ascending k, starting from +0;
+ *   - the segment sums are added in ascending order with plain fp32 adds, then bias[j] is added
+ *     (when bias != NULL), then the activation (AZ_ACT_NONE or AZ_ACT_RELU) is applied.
+ * M sizes the launch (the grid, and blocks of 1 / 2 / 4 waves for <= 32 / <= 64 / more rows) and
+ * masks loads and stores, nothing else: row i's bits do not depend on M or on i, and a CPU loop over
+ * the plan with a correctly rounded fmaf reproduces every value (a result of -0 may come out as
+ * +0).  No atomics.  Rows past M / N and k past K contribute nothing whatever
+ * the memory behind the operands holds (they are zeroed in LDS, not loaded).
+ * M >= 0 (0: nothing to do), N % 4 == 0, K % 4 == 0; lda, ldw, ldc % 4 == 0; A, W, bias, C and ws
+ * 16-byte aligned.  ws >= az_gemm_exact_ws_bytes(M, N, K): room for the S segment sums of a call
+ * whose tile grid alone cannot fill the GPU (0 for a call that needs none, or a rejected shape).
+ * --------------------------------------------------------------------------------- */
+#define AZ_EXACT_MAX_SEGMENTS 16
+int az_gemm_exact_plan(int N, int K, int* segments, int* seg_len);
+size_t az_gemm_exact_ws_bytes(int M, int N, int K);
+int az_gemm_exact_f32(const float* A, int lda, const float* W, int ldw, const float* bias, int act,
+                      float* C, int ldc, int M, int N, int K, void* ws, size_t ws_bytes,
+                      void* stream);
+
+/* The leaf evaluation of az_c4_eval_fwd / az_c4n_eval_fwd / az_c4r_eval_fwd / az_ttt_eval_fwd, for
+ * the same networks, as ONE host call whose launch sequence is the same at B = 1 and B = 4096:
+ * the board's fused trunk (az_c4_trunk_fwd, az_c4n_trunk_fwd, az_c4r_trunk_fwd, az_ttt_trunk_fwd),
+ * every nn.Linear the reference computes as az_gemm_exact_f32 -- fc1 / fc2 (TicTacToe),
+ * output_transform.0 and output_transform.2 as two real GEMMs, no composed heads -- and the
+ * policy / value heads one workgroup per row.  Every row of pi, v, gpi, gv is bit-identical to the
+ * same board evaluated alone or at any other position of any other batch. */
+#define AZ_EXACT_C4 0
+#define AZ_EXACT_TTT 1
+typedef struct az_eval_exact {
+  int game;                                /* AZ_EXACT_C4 or AZ_EXACT_TTT */
+  int nx; int ny;                          /* columns, rows (TicTacToe: nx = ny = n) */
+  int A;                                   /* actions (fc_policy rows), <= 32 */
+  int F;                                   /* Connect4: 64 nx ny; TicTacToe: 128 (n-2)^2 */
+  const float* conv1_w; const float* conv1_b; const float* conv2_w; const float* conv2_b;
+  const float* conv3_w; const float* conv3_b;          /* TicTacToe only */
+  const float* fc1_w; const float* fc1_b;  /* TicTacToe only: [512][F], [512] */
+  const float* fc2_w; const float* fc2_b;
+  const float* fc_policy_w; const float* fc_policy_b;  /* [A][F] (TicTacToe: [A][512]), [A] */
+  const float* fc_value_w; const float* fc_value_b;
+  const float* ot0_w; const float* ot0_b;  /* output_transform.0 [F][F], [F] */
+  const float* ot2_w; const float* ot2_b;  /* output_transform.2; all four NULL: no GNN tail */
+  int max_B;                               /* capacity of the scratch below */
+  float* feat;                             /* device [max_B][F] */
+  float* h1; float* h2;                    /* device [max_B][512] each (TicTacToe only) */
+  float* hidden; float* y;                 /* device [max_B][F] each (GNN tail only) */
+  float* logp; float* glogp;               /* device [max_B][A] */
+  void* ws; size_t ws_bytes;               /* >= az_eval_exact_ws_bytes(max_B, game, nx, ny, A) */
+} az_eval_exact;
+/* 0 for a shape az_eval_exact_fwd rejects. */
+size_t az_eval_exact_ws_bytes(int max_B, int game, int nx, int ny, int A);
+/* v != NULL: standard heads into pi [B][A] (may be NULL) and v [B];  gv != NULL: the GNN tail
+ * into gpi / gv; at least one of them.  boards int8 [B][nx][ny]; boards, pi, v, gpi, gv may be
+ * az_host_alloc memory.  0 <= B <= max_B (0: nothing to do; a caller with more rows calls again
+ * on the next max_B rows, which invariance makes the same result).  A board without a fused
+ * trunk, A > 32, a wrong F, B > max_B, a null pointer or a small workspace returns AZ_EINVAL with
+ * a message before anything is launched. */
+int az_eval_exact_fwd(const az_eval_exact* e, const int8_t* boards, int B, float* pi, float* v,
+                      float* gpi, float* gv, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * FrozenLakeNet (frozenlake/FrozenLakeNet.py:253-335): a leaf is a list of n = 1..5 node boards
  * (the board itself, then the next state of every valid action), S = N*N floats each:
  *   h_j  = relu(fe2 relu(fe0 x_j))                       feature_extractor, per node, hidden 128
