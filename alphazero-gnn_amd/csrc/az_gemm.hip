@@ -198,7 +198,18 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& p, Acc (&acc)[TI][
         const int row = r0 + rl, col = c0 + cc * 32 + c4;
         if (skip && v[0] == v[0]) continue;
         if (slab) {
-          if (row < p.M && col < p.N) *reinterpret_cast<f32x4*>(slab + (size_t)row * p.N + col) = v;
+          // write-through (sc1) 16-byte stores: the slab leaves the XCD's L2 as it is written
+          // instead of waiting dirty for the end-of-kernel write-back in front of the reduce
+          // launch (B = 512: gemm_p3 32.1 -> 31.3 us, the reduce launch unchanged:
+          // profiles/reduce_heads/README.md).  Wave-uniform base at the wave tile's first row;
+          // the offset stays below 256 rows x N x 4 bytes
+          if (row < p.M && col < p.N) {
+            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                slab + (size_t)__builtin_amdgcn_readfirstlane(r0) * p.N, 0, 0x7fffffff, 0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs,
+                                                   (rl * p.N + col) * 4, 0, 16);
+          }
         } else {
           epilogue_store4(p, row, col, v);
         }

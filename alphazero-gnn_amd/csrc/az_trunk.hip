@@ -830,8 +830,9 @@ __global__ __launch_bounds__(512) void splitk_heads_rows_kernel(
 // chunk-order finalize exactly as splitk_heads_partial_kernel + heads_finalize_kernel.
 // Body of the R-rows-per-block heads kernels: wave c owns chunk c (blockDim = 64 * nchunks),
 // keeps that chunk's head weights in registers for the block's R rows, and gets the rows' x / y
-// float4s from load(i, kc, x, y) (all of them issued before the first FMA); then the chunk-order
-// finalize for the R rows.
+// float4s from load(i, kc, x, y) (the weights are requested after load returns: a second round
+// trip when load itself waits on memory, as the split-K forms' slab sums do); then the
+// chunk-order finalize for the R rows.
 template <int AMAX, int R, typename Load>
 __device__ __forceinline__ void heads_rowsw_body(int B, int K, const float* __restrict__ wp,
                                                  int A, const float* __restrict__ wv,
@@ -953,7 +954,8 @@ __global__ __launch_bounds__(1024) void splitk_heads_rowsw_kernel(
 // composed_heads: wp / wv / bp / bv are rows of Wc / bc): a row's slabs are summed in slab order
 // from 0.f, then bias and activation -- splitk_reduce4_kernel's arithmetic, so the hidden rows'
 // bits are splitk_reduce's -- and feed heads_rowsw_body as heads_rowsw_kernel's x rows would;
-// `h` (may be null: the evaluator never reads the hidden rows) receives them.
+// `h` (may be null: the evaluator never reads the hidden rows) receives them.  Tuning build only
+// (AZ_SPLITK_HEADS_MODE=old): the bit reference of splitk_act_heads_kernel below.
 template <int AMAX, int S, int R>
 __global__ __launch_bounds__(1024) void splitk_act_heads_rowsw_kernel(
     const float* __restrict__ slab, int B, int K, const float* __restrict__ bias, int act,
@@ -988,6 +990,112 @@ __global__ __launch_bounds__(1024) void splitk_act_heads_rowsw_kernel(
       ys[i] = x;
     }
   });
+}
+
+// splitk_act_heads_rowsw_kernel's arithmetic, operand for operand, on a shorter dependent chain
+// (at B = 512 every block is resident at once, so the launch lasts one block's chain):
+//   - one memory round trip: the R rows' slab loads, the chunk's AMAX + 1 head-weight float4s,
+//     the bias and the tail's bp / bv are all requested before the first wait (the rowsw body
+//     asks for its weights only after the slab sums);
+//   - the activation (ACT) and the hidden rows' store (WANT_H) are compiled in;
+//   - one block barrier: behind it wave 2 i finishes row i's policy and wave 2 i + 1 its value
+//     (modulo the block's waves), each lane reading its column's 16 chunk slots at once and
+//     adding the row's chunks in chunk order from 0.f.  Lane a owns logit a: the max and the
+//     sum of the exponentials run over the lanes' values in ascending a as the one-lane loops
+//     did (readlane), each lane takes its own expf and stores its own log pi / pi.
+// blockDim = 64 * nchunks <= 1024; bias, bp, bv non-null.
+template <int AMAX, int S, int R, int ACT, bool WANT_H>
+__global__ __launch_bounds__(1024) void splitk_act_heads_kernel(
+    const float* __restrict__ slab, int B, int K, const float* __restrict__ bias,
+    float* __restrict__ h, const float* __restrict__ wp, int A, const float* __restrict__ wv,
+    const float* __restrict__ bp, const float* __restrict__ bv, float* __restrict__ logp,
+    float* __restrict__ pi, float* __restrict__ v) {
+  constexpr int PW = AMAX + 1;
+  constexpr int LOGV = AMAX == 8 ? 3 : (AMAX == 16 ? 4 : 5);
+  __shared__ float part[R][16][PW];
+  const int lane = threadIdx.x & 63, c = threadIdx.x >> 6;
+  const int nchunks = blockDim.x >> 6;
+  const int r0 = blockIdx.x * R;
+  const int k = c * HEADS_KC + lane * 4;
+  const bool kin = k < K;
+  const int kc = kin ? k : 0;
+  const size_t plane = (size_t)B * K;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  f32x4 sv[R][S], w[AMAX + 1];
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const size_t off = (size_t)min(r0 + i, B - 1) * K + kc;
+#pragma unroll
+    for (int q = 0; q < S; ++q) sv[i][q] = *reinterpret_cast<const f32x4*>(slab + q * plane + off);
+  }
+#pragma unroll
+  for (int a = 0; a < AMAX; ++a)
+    w[a] = *reinterpret_cast<const f32x4*>(wp + (size_t)min(a, A - 1) * K + kc);
+  w[AMAX] = *reinterpret_cast<const f32x4*>(wv + kc);
+  const f32x4 bb = *reinterpret_cast<const f32x4*>(bias + kc);
+  const float bpa = bp[min(lane, A - 1)], bv0 = bv[0];
+#pragma unroll
+  for (int a = 0; a < AMAX; ++a) w[a] = (a < A && kin) ? w[a] : z;
+  w[AMAX] = kin ? w[AMAX] : z;
+#pragma unroll
+  for (int i = 0; i < R; ++i) {
+    const int row = r0 + i;
+    if (row >= B) break;
+    f32x4 x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float t = 0.f;
+#pragma unroll
+      for (int q = 0; q < S; ++q) t += sv[i][q][e];
+      t += bb[e];
+      x[e] = kin ? apply_act(t, ACT) : 0.f;
+    }
+    if constexpr (WANT_H)
+      if (kin) *reinterpret_cast<f32x4*>(h + (size_t)row * K + k) = x;
+    float pv[AMAX];
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+      pv[a] = fmaf(x[3], w[a][3], fmaf(x[2], w[a][2], fmaf(x[1], w[a][1], x[0] * w[a][0])));
+    const float ps = wave_multi_sum<AMAX>(pv);
+    const float vs = wave_sum_x(
+        fmaf(x[3], w[AMAX][3], fmaf(x[2], w[AMAX][2], fmaf(x[1], w[AMAX][1], x[0] * w[AMAX][0]))));
+    const int a = lane >> (6 - LOGV);
+    if ((lane & ((1 << (6 - LOGV)) - 1)) == 0 && a < A) part[i][c][a] = ps;
+    if (lane == 0) part[i][c][A] = vs;
+  }
+  __syncthreads();
+  // unit 2 i = row i's policy, 2 i + 1 its value; u is wave-uniform (scalar branches)
+  for (int u = __builtin_amdgcn_readfirstlane(c); u < 2 * R; u += nchunks) {
+    const int i = u >> 1, row = r0 + i;
+    if (row >= B) break;
+    const int col = (u & 1) ? A : min(lane, A - 1);
+    float t[16];   // slots past nchunks hold whatever LDS held: read, never added
+#pragma unroll
+    for (int cc = 0; cc < 16; ++cc) t[cc] = part[i][cc][col];
+    float s = 0.f;
+#pragma unroll
+    for (int cc = 0; cc < 16; ++cc)
+      if (cc < nchunks) s += t[cc];
+    if (u & 1) {
+      if (lane == 0) v[row] = tanhf(s + bv0);
+      continue;
+    }
+    const float l = s + bpa;
+    float mx = -INFINITY;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+      if (a < A) mx = fmaxf(mx, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(l), a)));
+    const float ex = expf(l - mx);
+    float se = 0.f;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+      if (a < A) se += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ex), a));
+    const float o = (l - mx) - logf(se);
+    if (lane < A) {
+      logp[(size_t)row * A + lane] = o;
+      if (pi) pi[(size_t)row * A + lane] = expf(o);
+    }
+  }
 }
 
 // Plain heads (x = hp rows, y = hv rows) with the same body: az_heads_fwd for B > 32, A <= 8.
@@ -1448,7 +1556,8 @@ static int linear_heads_impl(const float* x, int B, int F, const float* w, const
   // one launch: splitk_heads_rowsw_kernel (AZ_SPLITK_HEADS_MODE = rows / chunks select the
   // one-row-per-block kernel / chunk partials + finalize for A/B runs)
   static const char* env_mode = tuning_env("AZ_SPLITK_HEADS_MODE");
-  const char mode = env_mode ? env_mode[0] : 'w';   // w: rowsw, r: rows, c: chunks + finalize
+  // w: rowsw, r: rows, c: chunks + finalize ("old" selects transform_heads_impl's kernel only)
+  const char mode = env_mode && env_mode[0] != 'o' ? env_mode[0] : 'w';
   const bool rows_mode = mode != 'c' && F <= SPLITK_ROWS_MAXK &&
                          (F + HEADS_KC - 1) / HEADS_KC <= HEADS_ROWS_MAXC;
   const int nch = (F + HEADS_KC - 1) / HEADS_KC;
@@ -1504,7 +1613,7 @@ static int linear_heads_impl(const float* x, int B, int F, const float* w, const
 // workspace's pre_region).  Composed heads (y == NULL, A <= 8, B > 64: what every evaluator
 // calls): output_transform.2 is never run -- when output_transform.0 leaves split-K slabs one
 // kernel reduces them and runs the heads composed with W2 on the rows
-// (splitk_act_heads_rowsw_kernel), else the GEMM writes the fp32 hidden rows and
+// (splitk_act_heads_kernel), else the GEMM writes the fp32 hidden rows and
 // linear_heads_impl runs the same heads on them.  Otherwise, when output_transform.0 leaves
 // split-K slabs and output_transform.2 takes the P2 path, the slabs' reduce also writes hidden's
 // planes into pre_region (splitk_reduce_split), so neither GEMM launches a split of its own.
@@ -1572,14 +1681,48 @@ static int transform_heads_impl(const float* x, int B, int F, const float* w0, c
       const float* bc = wc + (size_t)(A + 1) * F;
       const float* sl = static_cast<const float*>(d.ws);
       float* h = hidden_scratch ? nullptr : hidden;
-      switch (S) {
+#ifdef AZ_TUNING   // AZ_SPLITK_HEADS_MODE=old: the kernel before splitk_act_heads_kernel (A/B runs,
+                   // and the bit reference of tests/test_gpu_reduce_heads.py)
+      static const char* env_mode = tuning_env("AZ_SPLITK_HEADS_MODE");
+      if (tuning_env("AZ_SPLITK_HEADS_PRINT"))   // the split count this call's GEMM left
+        fprintf(stderr, "splitk_act_heads B=%d F=%d A=%d S=%d h=%d\n", B, F, A, S, h != nullptr);
+      if (env_mode && env_mode[0] == 'o') {
+        switch (S) {
 #define AZ_SKA(SS) case SS: hipLaunchKernelGGL((splitk_act_heads_rowsw_kernel<8, SS, 1>), dim3(B), \
                                  dim3(64 * nch), 0, s, sl, B, F, b0, (int)AZ_ACT_RELU, h, wc, A,     \
                                  wc + (size_t)A * F, bc, bc + A, logp, pi, v); break;
-        AZ_SKA(2) AZ_SKA(3) AZ_SKA(4) AZ_SKA(5) AZ_SKA(6) AZ_SKA(7) default: AZ_SKA(8)
+          AZ_SKA(2) AZ_SKA(3) AZ_SKA(4) AZ_SKA(5) AZ_SKA(6) AZ_SKA(7) default: AZ_SKA(8)
 #undef AZ_SKA
+        }
+        return check_launch("splitk_act_heads_rowsw_kernel");
       }
-      return check_launch("splitk_act_heads_rowsw_kernel");
+#endif
+      // rows per block (the same bits for either): one while every block gets a CU of its own,
+      // two above that -- half the blocks, so half the reads of the 113 KB of head weights
+      // (B = 128 / 256: 31.5 / 37.6 us per step with one row against 32.6 / 38.4 with two;
+      // B = 384 / 512: 47.7 / 49.6 against 46.2 / 48.6: profiles/reduce_heads/README.md);
+      // AZ_SPLITK_HEADS_R = 1 / 2 (tuning build) forces one
+      static int cus = 0;
+      if (cus <= 0) {
+        int dev = 0, n = 0;
+        cus = (hipGetDevice(&dev) == hipSuccess &&
+               hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+               n > 0) ? n : 256;
+      }
+      static const char* env_r = tuning_env("AZ_SPLITK_HEADS_R");
+      const int R = env_r && (atoi(env_r) == 1 || atoi(env_r) == 2) ? atoi(env_r) : B > cus ? 2 : 1;
+      const dim3 g((B + R - 1) / R), blk(64 * nch);
+#define AZ_SKH(SS, RR, HH) hipLaunchKernelGGL(                                                  \
+    (splitk_act_heads_kernel<8, SS, RR, AZ_ACT_RELU, HH>), g, blk, 0, s, sl, B, F, b0, h, wc, A, \
+    wc + (size_t)A * F, bc, bc + A, logp, pi, v)
+#define AZ_SKA(SS) case SS: if (R == 2 && h) AZ_SKH(SS, 2, true); else if (R == 2) AZ_SKH(SS, 2, false); \
+                            else if (h) AZ_SKH(SS, 1, true); else AZ_SKH(SS, 1, false); break;
+      switch (S) {
+        AZ_SKA(2) AZ_SKA(3) AZ_SKA(4) AZ_SKA(5) AZ_SKA(6) AZ_SKA(7) default: AZ_SKA(8)
+      }
+#undef AZ_SKA
+#undef AZ_SKH
+      return check_launch("splitk_act_heads_kernel");
     }
     if ((rc = splitk_reduce(&d, S, s))) return rc;
   } else if (S > 1) {
