@@ -123,9 +123,11 @@ class Coach:
                                                        and _flag(args, "gnn_neighbors")):
             raise ValueError("gnn_neighbors_train trains the GNN on the child stars gnn_neighbors "
                              "evaluates: it needs both use_gnn and gnn_neighbors")
-        if _flag(args, "batch_invariant") and _flag(args, "gnn_neighbors"):
-            # the packed-star kernels go through az_gemm_f32's dispatch, which picks its tile by
-            # the row count: there is no invariant form of them yet
+        if (_flag(args, "batch_invariant") and _flag(args, "gnn_neighbors")
+                and not getattr(nnet, "batch_invariant_stars", False)):
+            # a network says so itself when its star entry points are invariant too (the GNN
+            # wrappers route them through az_star_eval_exact_fwd); the default packed-star
+            # kernels go through az_gemm_f32's dispatch, which picks its tile by the row count
             raise ValueError("batch_invariant cannot be combined with gnn_neighbors (with or "
                              "without gnn_neighbors_lockstep): the star evaluation is not "
                              "batch-invariant")

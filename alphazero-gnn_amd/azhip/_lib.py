@@ -122,6 +122,22 @@ class EvalExact(ctypes.Structure):
                  ("ws", c_void_p), ("ws_bytes", c_size_t)])
 
 
+class GemmExactDesc(ctypes.Structure):
+    """az_gemm_exact_desc (include/az_hip.h)."""
+    _fields_ = [("M", c_int), ("N", c_int), ("K", c_int), ("A", c_void_p), ("lda", c_int),
+                ("W", c_void_p), ("ldw", c_int), ("bias", c_void_p), ("act", c_int),
+                ("C", c_void_p), ("ldc", c_int), ("W2", c_void_p), ("bias2", c_void_p),
+                ("act2", c_int), ("C2", c_void_p), ("R", c_void_p), ("ldr", c_int),
+                ("G", c_void_p), ("ldg", c_int), ("ws", c_void_p), ("ws_bytes", c_size_t)]
+
+
+class StarEvalExact(ctypes.Structure):
+    """az_star_eval_exact (include/az_hip.h)."""
+    _fields_ = [("e", EvalExact), ("L", c_int), ("H", c_int),
+                ("layers", LayerW * STAR_MAX_LAYERS), ("max_V", c_int), ("leaf", c_void_p),
+                ("x0", c_void_p)]
+
+
 FL_MAX_LAYERS = 4
 
 
@@ -201,6 +217,16 @@ SIGNATURES = {
     "az_eval_exact_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "az_eval_exact_fwd": (c_int, [ctypes.POINTER(EvalExact), c_void_p, c_int, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
+    "az_gemm_exact_ex_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "az_gemm_exact_ex": (c_int, [ctypes.POINTER(GemmExactDesc), c_void_p]),
+    "az_gnn_star_batch_exact_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "az_gnn_star_batch_exact_infer": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                              c_int, ctypes.POINTER(LayerW), c_void_p, c_void_p,
+                                              c_size_t, c_void_p]),
+    "az_star_eval_exact_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                               c_int]),
+    "az_star_eval_exact_fwd": (c_int, [ctypes.POINTER(StarEvalExact), c_void_p, c_void_p, c_int,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "az_fl_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "az_fl_eval_fwd": (c_int, [ctypes.POINTER(FlEval), c_void_p, c_void_p, c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p]),

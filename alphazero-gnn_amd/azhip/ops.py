@@ -484,6 +484,39 @@ def linear_exact(x, w, b=None, act=ACT_NONE, out=None, M=None, ws=None):
     return out
 
 
+def linear_exact_ex(x, w, b=None, act=ACT_NONE, out=None, M=None, ws=None, w2=None, b2=None,
+                    act2=ACT_NONE, out2=None, R=None, G=None):
+    """az_gemm_exact_ex: linear_exact with the node update's epilogues.  act may also be
+    ACT_SIGMOID; R and G (row strides from the tensors) make the gated residual out = fma(G, x w^T
+    + b, R); w2 (with b2, act2, out2) pairs a second [N, K] product on the same x in the same
+    launch.  Every output has the bits of a separate call at any M.  Returns out, or (out, out2)
+    for a paired call."""
+    for t, n in ((x, "x"), (w, "w"), (w2, "w2"), (R, "R"), (G, "G")):
+        _need(t, name=n)
+    M = x.shape[0] if M is None else M
+    N, K = w.shape
+    if w2 is not None and (tuple(w2.shape) != (N, K) or w2.stride(0) != w.stride(0)):
+        raise ValueError("linear_exact_ex: w2 must have w's shape and row stride")
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=torch.float32)
+    if w2 is not None and out2 is None:
+        out2 = torch.empty((M, N), device=x.device, dtype=torch.float32)
+    if out2 is not None and out2.stride(0) != out.stride(0):
+        raise ValueError("linear_exact_ex: out2 must have out's row stride")
+    L = _lib.lib()
+    nb = int(L.az_gemm_exact_ex_ws_bytes(M, N, K, int(w2 is not None)))
+    if ws is None and nb:
+        ws = workspace(x.device, max(nb, 64 << 20))
+    P = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    d = _lib.GemmExactDesc(M, N, K, P(x), x.stride(0), P(w), w.stride(0), P(b), act, P(out),
+                           out.stride(0), P(w2), P(b2), act2, P(out2), P(R),
+                           R.stride(0) if R is not None else 0, P(G),
+                           G.stride(0) if G is not None else 0, P(ws),
+                           ws.numel() if ws is not None else 0)
+    _lib.check(L.az_gemm_exact_ex(ctypes.byref(d), _stream()), "az_gemm_exact_ex")
+    return out if w2 is None else (out, out2)
+
+
 def exact_board(w_net):
     """(game, cols, rows) of az_eval_exact for a board network (nets.Connect4Net /
     nets.TicTacToeNet), or None when the board has no fused trunk."""
@@ -614,6 +647,94 @@ def gnn_star_batch_infer(x, offs, layers, out=None, ws=None, H=128, stream=None)
                                          ctypes.c_size_t(ws.numel()), s),
                "az_gnn_star_batch_infer")
     return out, ws
+
+
+def gnn_star_batch_exact_ws_bytes(B, V, F, num_layers, H=128):
+    """az_gnn_star_batch_exact_ws_bytes (no GPU work)."""
+    return int(_lib.load().az_gnn_star_batch_exact_ws_bytes(B, V, F, H, num_layers))
+
+
+def gnn_star_batch_exact_infer(x, offs, layers, out=None, ws=None, H=128, stream=None):
+    """az_gnn_star_batch_exact_infer: gnn_star_batch_infer's arguments and result with every
+    product an exact GEMM, so out[b] is the same bits whatever else is packed with star b.
+    Returns (out, ws)."""
+    _need(x, name="x")
+    _need(offs, torch.int32, "offs")
+    V, F = x.shape
+    B = offs.numel() - 1
+    if not x.is_contiguous():
+        raise ValueError("gnn_star_batch_exact_infer: x must be contiguous")
+    L = _lib.lib()
+    if isinstance(layers, ctypes.Array):
+        lw, nl = layers, len(layers)
+    else:
+        nl = len(layers)
+        lw = (LayerW * max(nl, 1))(*[layer_weights(Wl) for Wl in layers])
+    nbytes = int(L.az_gnn_star_batch_exact_ws_bytes(B, V, F, H, nl)) if B > 0 else 0
+    if B > 0 and nbytes == 0:
+        raise ValueError(f"az_gnn_star_batch_exact_infer: unsupported shape B={B} V={V} F={F} "
+                         f"H={H} L={nl}")
+    dev = _dev(x)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    out = torch.empty((max(B, 0), F), device=dev) if out is None else out
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(L.az_gnn_star_batch_exact_infer(_p(x), _p(offs), B, V, F, H, nl, lw, _p(out),
+                                               _p(ws), ctypes.c_size_t(ws.numel()), s),
+               "az_gnn_star_batch_exact_infer")
+    return out, ws
+
+
+class StarEvalExact:
+    """az_star_eval_exact descriptor with its device scratch for up to max_B stars of max_V packed
+    rows: W the board network's parameter tensors, G the PolicyValueGNN's, board = (game, cols,
+    rows) as exact_board returns it, num_layers the GNNLayers.  The tensors are read through the
+    pointers taken here, so they must be updated in place."""
+
+    def __init__(self, W, G, board, A, num_layers, max_B, max_V, device, H=128):
+        game, nx, ny = board
+        ttt = game == _lib.EXACT_TTT
+        F = 128 * (nx - 2) * (ny - 2) if ttt else 64 * nx * ny
+        self.board, self.A, self.F, self.L = board, A, F, num_layers
+        self.max_B, self.max_V = max_B, max_V
+        nb = int(_lib.lib().az_star_eval_exact_ws_bytes(max_B, max_V, game, nx, ny, A, num_layers,
+                                                        H))
+        if nb == 0:
+            raise ValueError(f"az_star_eval_exact: unsupported shape game={game} cols={nx} "
+                             f"rows={ny} A={A} L={num_layers} max_B={max_B} max_V={max_V}")
+        e = lambda *s: torch.empty(s, device=device, dtype=torch.float32)  # noqa: E731
+        self.feat = e(max_V, F)
+        self.h1 = e(max_B, 512) if ttt else None
+        self.h2 = e(max_B, 512) if ttt else None
+        self.hidden, self.y, self.leaf, self.x0 = (e(max_B, F) for _ in range(4))
+        self.logp, self.glogp = e(max_B, A), e(max_B, A)
+        self.ws = torch.empty((nb,), dtype=torch.uint8, device=device)
+        P = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        names = ("conv1", "conv2", "conv3", "fc1", "fc2", "fc_policy", "fc_value")
+        have = set(W.keys())
+        wts = [P(W[f"{l}.{k}"]) if f"{l}.{k}" in have else None
+               for l in names for k in ("weight", "bias")]
+        ot = [P(G[f"output_transform.{i}.{k}"]) for i in (0, 2) for k in ("weight", "bias")]
+        d = self.desc = _lib.StarEvalExact()
+        d.e = _lib.EvalExact(game, nx, ny, A, F, *wts, *ot, max_B, P(self.feat), P(self.h1),
+                             P(self.h2), P(self.hidden), P(self.y), P(self.logp), P(self.glogp),
+                             P(self.ws), nb)
+        d.L, d.H, d.max_V = num_layers, H, max_V
+        for i in range(num_layers):
+            d.layers[i] = LayerW(*[P(G[f"layers.{i}.{k}"]) for k in LAYER_KEYS])
+        d.leaf, d.x0 = P(self.leaf), P(self.x0)
+        self._keep = (W, G)
+
+
+def star_eval_exact(ev, rows_i8, offs, B, V, pi=None, v=None, gpi=None, gv=None, stream=None):
+    """az_star_eval_exact_fwd on `ev` (a StarEvalExact): B stars packed in the first V rows of
+    rows_i8 [*, cols, rows], offs int32 [B+1] -> pi [B][A], v [B] of the leaf boards and gpi
+    [B][A], gv [B] of the stars; device tensors or HostBuffer views.  Queued on `stream` (default:
+    the current stream); nothing is synchronised."""
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(_lib.lib().az_star_eval_exact_fwd(ctypes.byref(ev.desc), _p(rows_i8), _p(offs), B,
+                                                 V, _p(pi), _p(v), _p(gpi), _p(gv), s),
+               "az_star_eval_exact_fwd")
 
 
 def gnn_star_batch_save_bytes(B, V, F, num_layers, H=128):

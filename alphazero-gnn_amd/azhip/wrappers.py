@@ -663,11 +663,12 @@ def _star_chunk_cost(F):
     return 8 * F + 1024 + 64, 28 * F + 1024 + 64, 42 << 20
 
 
-def star_chunks(offs, F, budget=None):
+def star_chunks(offs, F, budget=None, cost=None):
     """Split B stars (offs int [B+1]) into consecutive runs [b0, b1) whose buffers stay under the
-    budget (STAR_CHUNK_BYTES); a run is at least one star."""
+    budget (STAR_CHUNK_BYTES); a run is at least one star.  cost: the route's (bytes per packed
+    row, bytes per star, fixed bytes), _star_chunk_cost(F) when None."""
     budget = STAR_CHUNK_BYTES if budget is None else budget
-    cr, cs, fixed = _star_chunk_cost(F)
+    cr, cs, fixed = _star_chunk_cost(F) if cost is None else cost
     B = len(offs) - 1
     lin = cr * np.asarray(offs, np.int64) + cs * np.arange(B + 1, dtype=np.int64)
     out, b0 = [], 0
@@ -785,6 +786,78 @@ class _StarBatch:
                 ops.gnn_star_batch_infer(feat, co, self.layers if nl else [], out=self.x0[:n],
                                          ws=self.ws, stream=s)
                 nets.gnn_per_row_heads(w.nnet, w.gnn, self.x0[:n], pi=gpi[b0:b1], v=gv[b0:b1])
+        ev = torch.cuda.Event()
+        ev.record(s)
+        return _PendingDirect(e, (pi, v, gpi, gv), ev, B)
+
+
+# The exact route's own budget (args.batch_invariant).  Per packed row: its features (4 F) and its
+# P row (2 H 4 = 1 KB); per star: TA (8 F), gate, u1, the next row 0, the leaf row, x0, hidden and
+# y (4 F each), its Pt row and the TicTacToe head rows (2 x 2 KB); fixed: the exact GEMMs' slabs,
+# which end at a row count (the projection's 3,968 rows x 14 segments x 1 KB = 57 MB at F = 3136,
+# the tail's 256 rows x 11 segments x 12.5 KB = 35 MB) -- 128 MB covers every board.  At F = 3136
+# that is 13.5 KB per row and 117 KB per star: 1 GiB holds about 3,800 stars of 9 boards.
+STAR_EXACT_CHUNK_BYTES = 1 << 30
+
+
+def _star_exact_chunk_cost(F):
+    """(bytes per packed row, bytes per star, fixed bytes) of STAR_EXACT_CHUNK_BYTES' derivation."""
+    return 4 * F + 1024 + 64, 36 * F + 1024 + 4096 + 256, 128 << 20
+
+
+class _StarExactBatch:
+    """predict_both_stars under args.batch_invariant, for one stream: ONE az_star_eval_exact_fwd
+    call per chunk (trunk, row-0 gather, standard tail, the exact layer stack, output_transform,
+    heads), packed stars read from and outputs written to mapped host memory (ops.HostBuffer, a
+    ring so that several batches can be in flight, _PendingDirect's ownership tokens).  Device
+    scratch is allocated once per capacity; a batch whose buffers would exceed
+    STAR_EXACT_CHUNK_BYTES runs as consecutive chunks on the same scratch, which changes no bits:
+    a star's rows are a function of the star alone."""
+
+    def __init__(self, w, stream=None):
+        self.w, self.stream = w, stream
+        self.capV = self.capB = 0
+        self.ring = []
+        self.ev = None
+        self.calls = []           # (B, V) of every chunk, newest last (tests read it)
+
+    def _grow(self, V, B):
+        w = self.w
+        capV = max(self.capV, (V + 1023) // 1024 * 1024)
+        capB = max(self.capB, (B + 255) // 256 * 256)
+        torch.cuda.synchronize(w.device)          # in-flight batches may use the old scratch
+        self.ev = ops.StarEvalExact(w.nnet.params, w.gnn.params, ops.exact_board(w.nnet),
+                                    w.action_size, w.gnn.num_layers, capB, capV, w.device)
+        self.capV, self.capB = capV, capB
+
+    _entry = _StarBatch._entry
+
+    def launch(self, rows, offs):
+        w, F = self.w, self.w.feature_dim
+        rows = np.asarray(rows)
+        offs = np.asarray(offs, dtype=np.int64)
+        B, V = len(offs) - 1, int(offs[-1])
+        if B < 1 or offs[0] != 0 or V != rows.shape[0] or np.any(np.diff(offs) < 1):
+            raise ValueError("predict_both_stars: offs must ascend from 0 to len(rows), one or "
+                             "more rows per star")
+        chunks = star_chunks(offs, F, STAR_EXACT_CHUNK_BYTES, _star_exact_chunk_cost(F))
+        mV = max(int(offs[b1] - offs[b0]) for b0, b1 in chunks)
+        mB = max(b1 - b0 for b0, b1 in chunks)
+        if mV > self.capV or mB > self.capB:
+            self._grow(mV, mB)
+        e = self._entry(V, B)
+        hin, hoffs, (pi, v, gpi, gv) = e["in"], e["offs"], e["out"]
+        hin.numpy()[:V] = rows.reshape(V, hin.shape[1], hin.shape[2])
+        ho = hoffs.numpy()
+        s = self.stream if self.stream is not None else torch.cuda.current_stream(w.device)
+        for c, (b0, b1) in enumerate(chunks):
+            v0, v1, n = int(offs[b0]), int(offs[b1]), b1 - b0
+            o0 = b0 + c                           # this chunk's rebased offs in the host buffer
+            ho[o0:o0 + n + 1] = offs[b0:b1 + 1] - v0
+            ops.star_eval_exact(self.ev, hin[v0:v1], hoffs[o0:o0 + n + 1], n, v1 - v0,
+                                pi=pi[b0:b1], v=v[b0:b1], gpi=gpi[b0:b1], gv=gv[b0:b1], stream=s)
+            self.calls.append((n, v1 - v0))
+        del self.calls[:-4096]
         ev = torch.cuda.Event()
         ev.record(s)
         return _PendingDirect(e, (pi, v, gpi, gv), ev, B)
@@ -1250,6 +1323,33 @@ class GNNWrapperMixin:
             return 1 << 30
         return 8 if _direct_ok(self) else 0
 
+    @property
+    def batch_invariant_stars(self):
+        """True when the star entry points (predict_with_gnn with neighbours, predict_star_batch,
+        predict_both_stars) are batch-invariant too: args.batch_invariant is set and the GNN has
+        at most ops.STAR_MAX_LAYERS layers, the most az_star_eval_exact_fwd takes.  Coach accepts
+        batch_invariant with gnn_neighbors only for a network that says so."""
+        return bool(self.batch_invariant and self.gnn.num_layers <= ops.STAR_MAX_LAYERS)
+
+    def _exact_stars(self, rows, offs, stream=None):
+        """args.batch_invariant: queue packed stars on the exact route (_StarExactBatch, one per
+        stream); .result() -> (pi, v, gpi, gv).  Never another route: more layers than the exact
+        evaluator takes is an error."""
+        if not self.batch_invariant_stars:
+            raise ValueError(f"{type(self).__name__}: batch_invariant evaluates stars through "
+                             f"az_star_eval_exact_fwd, which takes at most {ops.STAR_MAX_LAYERS} "
+                             f"GNN layers, not {self.gnn.num_layers}")
+        self.nnet.eval()
+        self.gnn.eval()
+        self._sync_params()
+        batches = self.__dict__.setdefault("_star_exact_batches", {})
+        key = None if stream is None else stream.cuda_stream
+        d = batches.get(key)
+        if d is None:
+            d = batches[key] = _StarExactBatch(self, stream)
+        self.star_route = "exact"
+        return d.launch(rows, offs)
+
     def predict(self, board):
         return NetWrapper.predict(self, board)
 
@@ -1310,13 +1410,21 @@ class GNNWrapperMixin:
         switches select nothing above 8 stars: measured end to end at 16 .. 2,048 stars of 8 nodes
         on 7x7, 7x6 and 4x4, the batched route beat the composition 1.17x - 3.4x, everywhere by
         more than the larger spread.  self.star_route names the route
-        taken."""
+        taken.  Under args.batch_invariant every call, of any number of stars of any size,
+        with or without the lock-step key and whatever AZ_B1_MODE / AZ_NO_ZEROCOPY say, takes
+        the exact star route ("exact"; ValueError when the GNN has more layers than it takes)."""
         self.nnet.eval()
         self.gnn.eval()
         self._sync_params()
         A = self.action_size
         if len(node_lists) == 0:
             return np.zeros((0, A), np.float32), np.zeros((0,), np.float32)
+        if self.batch_invariant:
+            rows = np.concatenate([np.asarray(nodes, dtype=np.int8).reshape(
+                len(nodes), self.board_x, self.board_y) for nodes in node_lists])
+            offs = np.concatenate([[0], np.cumsum([len(nodes) for nodes in node_lists])])
+            _, _, gpi, gv = self._exact_stars(rows, offs).result()
+            return gpi, gv
         small = (len(node_lists) <= ops.STAR_MAX_STARS
                  and max(len(nodes) for nodes in node_lists) <= ops.STAR_MAX_NODES)
         if self._star_direct_ok() and small:
@@ -1348,6 +1456,8 @@ class GNNWrapperMixin:
         """predict_both_stars without waiting: .result() -> (pi, v, gnn_pi, gnn_v).  stream: run
         on that HIP stream with its own device scratch (the lock-step lanes give each lane one);
         the caller orders the stream after any parameter update."""
+        if self.batch_invariant:
+            return self._exact_stars(rows, offs, stream)
         self.nnet.eval()
         self.gnn.eval()
         self._sync_params()
@@ -1361,7 +1471,10 @@ class GNNWrapperMixin:
         rows, az_gnn_star_batch_infer, output_transform and the heads on the row 0s; one host copy
         out -> (pi [B][A], v [B], gnn_pi [B][A], gnn_v [B]).  Rows are within 1e-5 of the
         batch-1 calls, not bit-identical to them, and a batch split by STAR_CHUNK_BYTES may differ
-        in bits from the unsplit one (the GEMM dispatch chooses its tile by the row count)."""
+        in bits from the unsplit one (the GEMM dispatch chooses its tile by the row count).
+        Under args.batch_invariant the call is az_star_eval_exact_fwd instead ("exact"): a star's
+        four rows are the same bits alone, in any batch and however the batch is chunked, pi / v
+        equal predict(leaf) and a one-row star's gnn_pi / gnn_v equal predict_with_gnn(leaf)."""
         return self.predict_both_stars_async(rows, offs).result()
 
     def predict_with_gnn(self, board, neighbor_states=None):

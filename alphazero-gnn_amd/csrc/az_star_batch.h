@@ -31,4 +31,19 @@ static inline bool star_batch_shape(int B, int V, int F, int H, int L) {
          H <= (1 << 16) && L >= 0 && L <= AZ_STAR_MAX_LAYERS && (size_t)V * F < (size_t(1) << 40);
 }
 
+// az_star_batch.hip's two kernels for the exact layer stack (az_star_exact.hip), which runs them
+// unchanged: TA[b] = [t | agg] of every star (t / Pt nullptr: the star's own row 0 and its P row),
+// and x0[b] = the star's row 0 for every star (all != 0) or for the one-row stars only.
+int star_batch_agg(const float* x, const int* offs, int B, int V, int F, int H, const float* P,
+                   const float* t, const float* Pt, const float* b1, const float* w2,
+                   const float* b2, float* TA, hipStream_t s);
+int star_batch_row0(const float* x, const int* offs, int B, int V, int F, int all, float* x0,
+                    hipStream_t s);
+// the argument checks of az_gnn_star_batch_infer after the shape rule (pointers, alignment, the
+// workspace size when L > 0, layer weights, a host offs that does not ascend from 0 to V); `who` names the entry point in the message
+int star_batch_check(const char* who, const float* x, const int* offs, int B, int V, int L,
+                     const az_gnn_layer_w* layers, const float* x0, const void* ws,
+                     size_t ws_bytes, size_t ws_need);
+int star_offs_check(const char* who, const int* offs, int B, int V);
+
 }  // namespace az

@@ -141,6 +141,59 @@ static StarBatchWs star_batch_ws(int B, int V, int F, int H) {
   return w;
 }
 
+int star_batch_agg(const float* x, const int* offs, int B, int V, int F, int H, const float* P,
+                   const float* t, const float* Pt, const float* b1, const float* w2,
+                   const float* b2, float* TA, hipStream_t s) {
+  hipLaunchKernelGGL(star_batch_agg_kernel, dim3((F + 1023) / 1024, B), dim3(256), 0, s, x, offs,
+                     V, F, H, P, t, Pt, b1, w2, b2, TA);
+  return check_launch("star_batch_agg_kernel");
+}
+
+int star_batch_row0(const float* x, const int* offs, int B, int V, int F, int all, float* x0,
+                    hipStream_t s) {
+  hipLaunchKernelGGL(star_batch_row0_kernel, dim3((F + 1023) / 1024, B), dim3(256), 0, s, x, offs,
+                     V, F, all, x0);
+  return check_launch("star_batch_row0_kernel");
+}
+
+int star_offs_check(const char* who, const int* offs, int B, int V) {
+  // offs in host memory the device maps (az_host_alloc, pinned) is checked here; offs in HBM is
+  // clamped by the kernels (star_span)
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, offs) != hipSuccess) {
+    (void)hipGetLastError();
+  } else if (attr.type == hipMemoryTypeHost) {
+    AZ_REQUIRE(offs[0] == 0 && offs[B] == V, AZ_EINVAL, "%s: offs[0]=%d offs[B]=%d (need 0 and "
+               "V=%d)", who, offs[0], offs[B], V);
+    for (int b = 0; b < B; ++b)
+      AZ_REQUIRE(offs[b + 1] > offs[b], AZ_EINVAL, "%s: offs not ascending at star %d (%d, %d)",
+                 who, b, offs[b], offs[b + 1]);
+  }
+  return AZ_OK;
+}
+
+int star_batch_check(const char* who, const float* x, const int* offs, int B, int V, int L,
+                     const az_gnn_layer_w* layers, const float* x0, const void* ws,
+                     size_t ws_bytes, size_t ws_need) {
+  AZ_REQUIRE(x && offs && x0 && (L == 0 || (layers && ws)), AZ_EINVAL, "%s: null pointer", who);
+  AZ_REQUIRE(aligned16(x) && aligned16(x0) && aligned16(ws) && ((uintptr_t)offs & 3u) == 0,
+             AZ_EINVAL, "%s: x, x0 and ws need 16B alignment, offs 4B alignment", who);
+  AZ_REQUIRE(x != x0, AZ_EINVAL, "%s: x0 may not alias x", who);
+  AZ_REQUIRE(L == 0 || ws_bytes >= ws_need, AZ_EINVAL,
+             "%s: workspace of %zu bytes too small (%zu needed)", who, ws_bytes, ws_need);
+  for (int l = 0; l < L; ++l) {
+    const az_gnn_layer_w& w = layers[l];
+    AZ_REQUIRE(w.att_w1 && w.att_b1 && w.att_w2 && w.att_b2 && w.upd_w1 && w.upd_b1 && w.upd_w2 &&
+                   w.upd_b2 && w.gate_w && w.gate_b,
+               AZ_EINVAL, "%s: null weight pointer in layer %d", who, l);
+    AZ_REQUIRE(aligned16(w.att_w1) && aligned16(w.upd_w1) && aligned16(w.upd_w2) &&
+                   aligned16(w.gate_w) && aligned16(w.upd_b1) && aligned16(w.upd_b2) &&
+                   aligned16(w.gate_b),
+               AZ_EINVAL, "%s: layer %d weights need 16B alignment", who, l);
+  }
+  return star_offs_check(who, offs, B, V);
+}
+
 }  // namespace az
 
 using namespace az;
@@ -158,39 +211,9 @@ extern "C" int az_gnn_star_batch_infer(const float* x, const int* offs, int B, i
              "H %% 4 == 0, 0 <= L <= %d)",
              B, V, F, H, L, AZ_STAR_MAX_LAYERS);
   if (B == 0) return AZ_OK;
-  AZ_REQUIRE(x && offs && x0 && (L == 0 || (layers && ws)), AZ_EINVAL,
-             "az_gnn_star_batch_infer: null pointer");
-  AZ_REQUIRE(aligned16(x) && aligned16(x0) && aligned16(ws) && ((uintptr_t)offs & 3u) == 0,
-             AZ_EINVAL,
-             "az_gnn_star_batch_infer: x, x0 and ws need 16B alignment, offs 4B alignment");
-  AZ_REQUIRE(x != x0, AZ_EINVAL, "az_gnn_star_batch_infer: x0 may not alias x");
-  AZ_REQUIRE(L == 0 || ws_bytes >= az_gnn_star_batch_ws_bytes(B, V, F, H, L), AZ_EINVAL,
-             "az_gnn_star_batch_infer: workspace of %zu bytes too small "
-             "(az_gnn_star_batch_ws_bytes)", ws_bytes);
-  for (int l = 0; l < L; ++l) {
-    const az_gnn_layer_w& w = layers[l];
-    AZ_REQUIRE(w.att_w1 && w.att_b1 && w.att_w2 && w.att_b2 && w.upd_w1 && w.upd_b1 && w.upd_w2 &&
-                   w.upd_b2 && w.gate_w && w.gate_b,
-               AZ_EINVAL, "az_gnn_star_batch_infer: null weight pointer in layer %d", l);
-    AZ_REQUIRE(aligned16(w.att_w1) && aligned16(w.upd_w1) && aligned16(w.upd_w2) &&
-                   aligned16(w.gate_w) && aligned16(w.upd_b1) && aligned16(w.upd_b2) &&
-                   aligned16(w.gate_b),
-               AZ_EINVAL, "az_gnn_star_batch_infer: layer %d weights need 16B alignment", l);
-  }
-  // offs in host memory the device maps (az_host_alloc, pinned) is checked here; offs in HBM is
-  // clamped by the kernels (star_span)
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, offs) != hipSuccess) {
-    (void)hipGetLastError();
-  } else if (attr.type == hipMemoryTypeHost) {
-    AZ_REQUIRE(offs[0] == 0 && offs[B] == V, AZ_EINVAL,
-               "az_gnn_star_batch_infer: offs[0]=%d offs[B]=%d (need 0 and V=%d)", offs[0],
-               offs[B], V);
-    for (int b = 0; b < B; ++b)
-      AZ_REQUIRE(offs[b + 1] > offs[b], AZ_EINVAL,
-                 "az_gnn_star_batch_infer: offs not ascending at star %d (%d, %d)", b, offs[b],
-                 offs[b + 1]);
-  }
+  int rc = star_batch_check("az_gnn_star_batch_infer", x, offs, B, V, L, layers, x0, ws, ws_bytes,
+                            az_gnn_star_batch_ws_bytes(B, V, F, H, L));
+  if (rc) return rc;
   hipStream_t s = as_stream(stream);
   const dim3 blk(256), grid((F + 1023) / 1024, B);
   if (L == 0) {
@@ -206,7 +229,6 @@ extern "C" int az_gnn_star_batch_infer(const float* x, const int* offs, int B, i
   float* u1 = reinterpret_cast<float*>(base + o.u1);
   float* tbuf = reinterpret_cast<float*>(base + o.tbuf);
   void* split = base + o.split;
-  int rc;
   for (int l = 0; l < L; ++l) {
     const az_gnn_layer_w& w = layers[l];
     float* t_out = l == L - 1 ? x0 : tbuf;

@@ -25,8 +25,9 @@ MI355X additions (absent from the reference; defaults reproduce its behaviour):
     --batch_invariant        a board's network outputs are the same bits whatever batch it rides in
                              (exact-fp32 GEMMs, az_eval_exact_fwd): the seed fixes the run, not the
                              seed together with --parallel_games and the rank count.  Slower than
-                             the default routes; not with --gnn_neighbors; config key
-                             batch_invariant
+                             the default routes.  With --gnn_neighbors (with or without
+                             --gnn_neighbors_lockstep) the stars take az_star_eval_exact_fwd, for
+                             --gnn_layers up to 4; config key batch_invariant
     multi-GPU: python -m torch.distributed.run --nproc-per-node P --master-addr 127.0.0.1 main.py ...
                (one rank per GPU, backend nccl = RCCL; episodes sharded by index)
 """
@@ -162,7 +163,8 @@ def parse(argv=None):
                         "on its own child star")
     p.add_argument("--batch_invariant", action="store_true", default=None,
                    help="evaluate every board with the same bits at any batch size (exact-fp32 "
-                        "GEMMs; slower; not with --gnn_neighbors)")
+                        "GEMMs; slower; with --gnn_neighbors also the star evaluation, "
+                        "--gnn_layers up to 4)")
     return p.parse_args(argv)
 
 

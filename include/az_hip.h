@@ -383,6 +383,32 @@ int az_gemm_exact_f32(const float* A, int lda, const float* W, int ldw, const fl
                       float* C, int ldc, int M, int N, int K, void* ws, size_t ws_bytes,
                       void* stream);
 
+/* az_gemm_exact_f32 with the epilogues of the GNN node update, arguments in a descriptor.  The
+ * segment chain and the plan are az_gemm_exact_f32's (az_gemm_exact_plan(N, K)); after "segment
+ * sums in ascending order, then bias" comes ONE of
+ *   act              AZ_ACT_NONE, AZ_ACT_RELU or AZ_ACT_SIGMOID (1 / (1 + expf(-v)));
+ *   gated residual   R and G non-NULL, act = AZ_ACT_NONE: C[i][j] = fmaf(G[i*ldg+j], v, R[i*ldr+j]),
+ *                    one rounding;
+ * and with W2 non-NULL the launch is PAIRED: a second weight matrix [N][K] (row stride ldw), bias2,
+ * act2 and output C2 (row stride ldc) share the A operand and the launch.  The plan is that of ONE
+ * product, so C and C2 hold the bits of two separate calls.  No gated residual on a paired call.
+ * Row i's bits depend on row i of A (and of R, G) and the weights only: not on M, not on i, not on
+ * whether the call ran spread over segments or direct.  Shapes, strides and alignment as
+ * az_gemm_exact_f32; ldr, ldg >= N and % 4 == 0; R, G, W2, bias2, C2 16-byte aligned.
+ * ws >= az_gemm_exact_ex_ws_bytes(M, N, K, paired). */
+typedef struct az_gemm_exact_desc {
+  int M; int N; int K;
+  const float* A; int lda;
+  const float* W; int ldw;
+  const float* bias; int act;
+  float* C; int ldc;
+  const float* W2; const float* bias2; int act2; float* C2;   /* the paired product, or all 0 */
+  const float* R; int ldr; const float* G; int ldg;           /* the gated residual, or all 0 */
+  void* ws; size_t ws_bytes;
+} az_gemm_exact_desc;
+size_t az_gemm_exact_ex_ws_bytes(int M, int N, int K, int paired);
+int az_gemm_exact_ex(const az_gemm_exact_desc* d, void* stream);
+
 /* The leaf evaluation of az_c4_eval_fwd / az_c4n_eval_fwd / az_c4r_eval_fwd / az_ttt_eval_fwd, for
  * the same networks, as ONE host call whose launch sequence is the same at B = 1 and B = 4096:
  * the board's fused trunk (az_c4_trunk_fwd, az_c4n_trunk_fwd, az_c4r_trunk_fwd, az_ttt_trunk_fwd),
@@ -744,6 +770,52 @@ size_t az_c4_star_eval_ws_bytes(int max_B, int nx, int ny, int A, int L);
  * alone.  A bad shape, a null pointer or a small workspace returns AZ_EINVAL before any launch. */
 int az_c4_star_eval_fwd(const az_c4_star_eval* e, const int8_t* boards, const int* counts, int B,
                         float* gpi, float* gv, void* stream);
+
+/* Batch-invariant star evaluation (config key batch_invariant with gnn_neighbors).
+ *
+ * az_gnn_star_batch_exact_infer: az_gnn_star_batch_infer's arguments, offs checks, shape limits
+ * and semantics (L = 0 gather and one-row stars included) with every product an exact GEMM: per
+ * layer P = x W1'^T (M = V, N = 2H, K = F; from layer 1 on also Pt over the B updated row 0s), the
+ * same weights-and-aggregate kernel, gate.0 and update_net.0 as ONE paired az_gemm_exact_ex launch
+ * on TA = [t | agg] (K = 2F; sigmoid -> gate, ReLU -> u1), update_net.2 with the gated-residual
+ * epilogue (R = TA's t half, G = gate).  x0[b] is a function of star b's rows and the weights
+ * only: the same bits at any B, V, position and packing, spread or direct.  Within 1e-5 of
+ * az_gnn_star_batch_infer, not bit-identical to it.
+ * ws >= az_gnn_star_batch_exact_ws_bytes(B, V, F, H, L) (0 for a rejected shape; monotonic in B and
+ * V, so a workspace sized for a capacity serves every smaller call). */
+size_t az_gnn_star_batch_exact_ws_bytes(int B, int V, int F, int H, int L);
+int az_gnn_star_batch_exact_infer(const float* x, const int* offs, int B, int V, int F, int H,
+                                  int L, const az_gnn_layer_w* layers, float* x0, void* ws,
+                                  size_t ws_bytes, void* stream);
+
+/* predict + predict_with_gnn(board, neighbor_states) of B leaves with their neighbourhoods as ONE
+ * host call, for every board az_eval_exact_fwd serves, with the same launch sequence at B = 1 and
+ * B = 4096: the board's fused trunk on the V packed rows, the gather of every star's row 0, the
+ * standard tail on the B leaf rows exactly as az_eval_exact_fwd runs it, the exact layer stack
+ * (az_gnn_star_batch_exact_infer), output_transform.0 / .2 as two exact GEMMs, the heads.
+ * A star's four output rows are the same bits alone, at any position of any pack and across
+ * calls; pi, v of star b equal az_eval_exact_fwd's pi, v of its leaf board; gpi, gv of a one-row
+ * star equal az_eval_exact_fwd's gpi, gv of that board. */
+typedef struct az_star_eval_exact {
+  az_eval_exact e;        /* game, shape, trunk / heads / output_transform weights (all of them);
+                             e.max_B: most stars a call may carry; e.feat: device [max_V][F];
+                             e.h1, e.h2, e.hidden, e.y, e.logp, e.glogp: [max_B] rows as there;
+                             e.ws >= az_star_eval_exact_ws_bytes(max_B, max_V, game, nx, ny, A, L, H) */
+  int L; int H;           /* GNN layers 0..4, attention.0's hidden width */
+  az_gnn_layer_w layers[AZ_STAR_MAX_LAYERS];   /* entries >= L unused */
+  int max_V;              /* most packed rows a call may carry, >= max_B */
+  float* leaf; float* x0; /* device [max_B][F] each */
+} az_star_eval_exact;
+/* 0 for a shape az_star_eval_exact_fwd rejects (a board without a fused trunk among them). */
+size_t az_star_eval_exact_ws_bytes(int max_B, int max_V, int game, int nx, int ny, int A, int L,
+                                   int H);
+/* rows int8 [V][nx][ny] packed stars, offs int32 [B+1] (star b = rows offs[b] .. offs[b+1]-1, row
+ * 0 the leaf), pi [B][A] and gpi [B][A] (each may be NULL), v [B], gv [B]; rows, offs and the
+ * outputs may be az_host_alloc memory.  0 <= B <= max_B, B <= V <= max_V (B == 0: nothing to do).
+ * A bad shape, a null pointer, a short workspace or a non-ascending host offs returns AZ_EINVAL
+ * with a message before any launch. */
+int az_star_eval_exact_fwd(const az_star_eval_exact* e, const int8_t* rows, const int* offs, int B,
+                           int V, float* pi, float* v, float* gpi, float* gv, void* stream);
 
 /* ---------------------------------------------------------------------------------
  * Backward pass (Connect4GNN.py:150-156,187-197 / TicTacToeGNN.py:217-264), deterministic:
