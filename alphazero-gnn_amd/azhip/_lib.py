@@ -108,6 +108,20 @@ class TttEval(ctypes.Structure):
                  ("glogp", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t)])
 
 
+TTT_STAR_MAX_NODES = 26
+
+
+class TttStarEval(ctypes.Structure):
+    """az_ttt_star_eval (include/az_hip.h)."""
+    _fields_ = ([(f"{l}_{k}", c_void_p) for l in ("conv1", "conv2", "conv3", "fc1", "fc2",
+                                                    "fc_policy", "fc_value", "ot0", "ot2")
+                 for k in "wb"] +
+                [("layers", LayerW * STAR_MAX_LAYERS), ("n", c_int), ("A", c_int), ("F", c_int),
+                 ("L", c_int), ("max_B", c_int), ("feat", c_void_p), ("x0", c_void_p),
+                 ("hidden", c_void_p), ("y", c_void_p), ("h1", c_void_p), ("h2", c_void_p),
+                 ("glogp", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t)])
+
+
 EXACT_MAX_SEGMENTS, EXACT_C4, EXACT_TTT = 16, 0, 1
 
 
@@ -205,6 +219,13 @@ SIGNATURES = {
     "az_c4_star_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "az_c4_star_eval_fwd": (c_int, [ctypes.POINTER(C4StarEval), c_void_p, c_void_p, c_int,
                                     c_void_p, c_void_p, c_void_p]),
+    "az_gnn_star_packed_infer_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "az_gnn_star_packed_infer": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                         ctypes.POINTER(LayerW), c_void_p, c_void_p, c_size_t,
+                                         c_void_p]),
+    "az_ttt_star_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "az_ttt_star_eval_fwd": (c_int, [ctypes.POINTER(TttStarEval), c_void_p, c_void_p, c_int,
+                                     c_int, c_void_p, c_void_p, c_void_p]),
     "az_ttt_trunk_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "az_ttt_eval_ws_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -842,6 +842,89 @@ def c4_star_eval(ev, boards_i8, counts, B, gpi=None, gv=None, stream=None):
                                               _p(gpi), _p(gv), s), "az_c4_star_eval_fwd")
 
 
+TTT_STAR_MAX_NODES = _lib.TTT_STAR_MAX_NODES
+
+
+def ttt_star_shape_ok(n):
+    """True for the board sides az_ttt_star_eval_fwd serves (a star of n x n boards has at most
+    n^2 + 1 <= 26 of them)."""
+    return 3 <= int(n) <= 5
+
+
+def gnn_star_packed_infer(x, offs, layers, out=None, ws=None, H=128, stream=None):
+    """az_gnn_star_packed_infer: x [V][F] packed star rows, offs int32 [B+1] (device tensor or
+    HostBuffer view; star b = rows offs[b] .. offs[b+1]-1, row 0 the leaf), B <= 8 stars of
+    <= 26 rows, layers a list of GNNLayer weight dicts -> out [B][F], row 0 of every star after
+    the layers in eval mode (gnn_utils.py:34-74), the same bits for a star alone and in any pack.
+    Returns (out, ws)."""
+    _need(x, name="x")
+    _need(offs, torch.int32, "offs")
+    V, F = x.shape
+    B = offs.numel() - 1
+    if not x.is_contiguous():
+        raise ValueError("gnn_star_packed_infer: x must be contiguous")
+    L = _lib.lib()
+    nl = len(layers)
+    nbytes = int(L.az_gnn_star_packed_infer_ws_bytes(B, F, H, nl)) if B > 0 else 0
+    if B > 0 and nbytes == 0:
+        raise ValueError(f"az_gnn_star_packed_infer: unsupported shape B={B} F={F} H={H} L={nl}")
+    dev = _dev(x)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty((max(nbytes, 256),), dtype=torch.uint8, device=dev)
+    out = torch.empty((max(B, 0), F), device=dev) if out is None else out
+    lw = (LayerW * max(nl, 1))(*[layer_weights(Wl) for Wl in layers])
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(L.az_gnn_star_packed_infer(_p(x), _p(offs), B, V, F, H, nl, lw, _p(out), _p(ws),
+                                          ctypes.c_size_t(ws.numel()), s),
+               "az_gnn_star_packed_infer")
+    return out, ws
+
+
+class TttStarEval:
+    """az_ttt_star_eval descriptor with its device scratch for up to max_B <= 8 stars of <= 26
+    boards of an n x n TicTacToeNet (ttt_star_shape_ok): W the net's parameter tensors, G the
+    PolicyValueGNN's, num_layers its GNNLayers.  The tensors are read through the pointers taken
+    here, so they must be updated in place."""
+
+    def __init__(self, W, G, n, A, num_layers, max_B, device):
+        n = int(n)
+        F = 128 * (n - 2) * (n - 2)
+        self.n, self.A, self.F, self.L, self.max_B = n, A, F, num_layers, max_B
+        nb = int(_lib.lib().az_ttt_star_eval_ws_bytes(max_B, n, A, num_layers))
+        if nb == 0:
+            raise ValueError(f"az_ttt_star_eval: unsupported shape n={n} A={A} L={num_layers} "
+                             f"max_B={max_B}")
+        e = lambda *s: torch.empty(s, device=device, dtype=torch.float32)  # noqa: E731
+        self.feat = e(max_B * TTT_STAR_MAX_NODES, F)
+        self.x0, self.hidden, self.y = e(max_B, F), e(max_B, F), e(max_B, F)
+        self.h1, self.h2, self.glogp = e(max_B, 512), e(max_B, 512), e(max_B, A)
+        self.ws = torch.empty((nb,), dtype=torch.uint8, device=device)
+        P = lambda t: t.data_ptr()  # noqa: E731
+        d = self.desc = _lib.TttStarEval()
+        for l in ("conv1", "conv2", "conv3", "fc1", "fc2", "fc_policy", "fc_value"):
+            for k in ("weight", "bias"):
+                setattr(d, f"{l}_{k[0]}", P(W[f"{l}.{k}"]))
+        for i in (0, 2):
+            for k in ("weight", "bias"):
+                setattr(d, f"ot{i}_{k[0]}", P(G[f"output_transform.{i}.{k}"]))
+        d.n, d.A, d.F, d.L, d.max_B = n, A, F, num_layers, max_B
+        for i in range(num_layers):
+            d.layers[i] = LayerW(*[P(G[f"layers.{i}.{k}"]) for k in LAYER_KEYS])
+        d.feat, d.x0, d.hidden, d.y = P(self.feat), P(self.x0), P(self.hidden), P(self.y)
+        d.h1, d.h2, d.glogp = P(self.h1), P(self.h2), P(self.glogp)
+        d.ws, d.ws_bytes = P(self.ws), nb
+        self._keep = (W, G)
+
+
+def ttt_star_eval(ev, rows_i8, offs, B, V, gpi=None, gv=None, stream=None):
+    """az_ttt_star_eval_fwd on `ev` (a TttStarEval): B stars packed in the first V rows of rows_i8
+    [*, n, n], offs int32 [B+1] -> gpi [B][A] (optional) and gv [B]; device tensors or HostBuffer
+    views.  Queued on `stream` (default: the current stream); nothing is synchronised."""
+    s = ctypes.c_void_p(stream.cuda_stream) if stream is not None else _stream()
+    _lib.check(_lib.lib().az_ttt_star_eval_fwd(ctypes.byref(ev.desc), _p(rows_i8), _p(offs), B, V,
+                                               _p(gpi), _p(gv), s), "az_ttt_star_eval_fwd")
+
+
 def heads(hp, wp, bp, wv, bv, hv=None, want_pi=True, logp=None, pi=None, v=None):
     """logp = log_softmax(hp wp^T + bp); v = tanh(hv wv^T + bv) (hv defaults to hp)."""
     hv = hp if hv is None else hv

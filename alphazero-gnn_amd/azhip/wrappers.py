@@ -649,6 +649,53 @@ class _StarDirect:
         return self.pi_np[:B].copy(), self.v_np[:B].copy()
 
 
+class _TttStarDirect:
+    """_StarDirect for TicTacToe: up to 8 leaves with their neighbourhoods (stars of <= n^2 + 1
+    boards, packed) as ONE C call (az_ttt_star_eval_fwd: the fused trunk, four launches per GNN
+    layer, output_transform, fc1 / fc2 and the heads) with zero-copy staging: packed rows and offs
+    are read and gpi / gv written in place in one mapped host buffer.  A star's outputs are
+    bit-identical to the same star evaluated alone."""
+
+    cap = ops.STAR_MAX_STARS
+
+    def __init__(self, w):
+        dev, A, cap = w.device, w.action_size, self.cap
+        n = w.nnet.n
+        self.nodes = n * n + 1
+        off = [0]
+        for nbytes in (cap * self.nodes * n * n, 4 * (cap + 1), 4 * cap * A, 4 * cap):
+            off.append(off[-1] + (nbytes + 255) // 256 * 256)
+        self.host = ops.HostBuffer(off[-1])
+        self.h_in = self.host.view(off[0], torch.int8, (cap * self.nodes, n, n))
+        self.h_offs = self.host.view(off[1], torch.int32, (cap + 1,))
+        self.h_pi = self.host.view(off[2], torch.float32, (cap, A))
+        self.h_v = self.host.view(off[3], torch.float32, (cap,))
+        self.h_in.zero_()
+        self.h_offs.zero_()
+        self.ev = ops.TttStarEval(w.nnet.params, w.gnn.params, n, A, w.gnn.num_layers, cap, dev)
+        self.in_np, self.offs_np = self.h_in.numpy(), self.h_offs.numpy()
+        self.pi_np, self.v_np = self.h_pi.numpy(), self.h_v.numpy()
+        self.fn = _lib.lib().az_ttt_star_eval_fwd
+        P = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        self.args = (ctypes.byref(self.ev.desc), P(self.h_in), P(self.h_offs))
+        self.outs = (P(self.h_pi), P(self.h_v))
+        self.stream = torch.cuda.current_stream(dev)
+        self.sptr = ctypes.c_void_p(self.stream.cuda_stream)
+
+    def run(self, node_lists):
+        """len(node_lists) <= 8 stars of <= n^2 + 1 boards each -> (gpi [B][A], gv [B]) copies."""
+        B, V = len(node_lists), 0
+        for b, nodes in enumerate(node_lists):
+            self.in_np[V:V + len(nodes)] = nodes
+            V += len(nodes)
+            self.offs_np[b + 1] = V
+        rc = self.fn(*self.args, B, V, *self.outs, self.sptr)
+        if rc:
+            _lib.check(rc, "az_ttt_star_eval_fwd")
+        self.stream.synchronize()
+        return self.pi_np[:B].copy(), self.v_np[:B].copy()
+
+
 # Device bytes one chunk of predict_both_stars may hold in the buffers that grow with the batch.
 # Per packed row: its features (4 F) and, in az_gnn_star_batch_infer's workspace, the fp16 planes
 # of the projection GEMM's A operand (4 F) and its P row (2 H 4 = 1 KB); per star: TA (8 F), gate,
@@ -1363,6 +1410,17 @@ class GNNWrapperMixin:
                 and os.environ.get("AZ_B1_MODE", "direct") == "direct"
                 and os.environ.get("AZ_NO_ZEROCOPY", "0") in ("", "0"))
 
+    def _ttt_star_direct_ok(self):
+        """The one-call TicTacToe star evaluator (az_ttt_star_eval_fwd) serves 3x3 .. 5x5 boards
+        under args.gnn_neighbors, the key of the mode that evaluates stars at inference: without
+        the key every route is what it was.  AZ_B1_MODE=graph or AZ_NO_ZEROCOPY=1 select the
+        composition, as they do for Connect4."""
+        return (_is_ttt(self) and ops.ttt_star_shape_ok(self.nnet.n)
+                and bool(nets._args_get(self.args, "gnn_neighbors", False))
+                and self.gnn.num_layers <= ops.STAR_MAX_LAYERS
+                and os.environ.get("AZ_B1_MODE", "direct") == "direct"
+                and os.environ.get("AZ_NO_ZEROCOPY", "0") in ("", "0"))
+
     def _star_compose(self, node_lists):
         """Any number of stars of any size on any wrapper: the trunk on every board, the layers on
         a forest-of-stars graph through the generic graph calls, output_transform and the heads on
@@ -1402,7 +1460,9 @@ class GNNWrapperMixin:
         (gpi float32[B][A], gv float32[B]): the heads of row 0 after PolicyValueGNN.forward on
         each star (Connect4GNN.py:86-120 on a star instead of a 1-row input).  Connect4 boards
         with a fused trunk, <= 9 nodes and <= 8 stars take the one-call evaluator ("onecall",
-        today's bits).  Under args.gnn_neighbors_lockstep -- the opt-in key of the batched mode;
+        today's bits); under args.gnn_neighbors so do TicTacToe 3x3 .. 5x5 boards with <= n^2 + 1
+        nodes and <= 8 stars (az_ttt_star_eval_fwd; without that key a TicTacToe star keeps the
+        composition).  Under args.gnn_neighbors_lockstep -- the opt-in key of the batched mode;
         without it every route is what it was -- more than 8 stars, or a star of more than 9
         nodes, takes predict_both_stars on every wrapper ("batched").  What is left takes the
         composition (<= 8 small stars on another wrapper, or under AZ_B1_MODE=graph /
@@ -1431,6 +1491,13 @@ class GNNWrapperMixin:
             d = self.__dict__.get("_star_direct")
             if d is None:
                 d = self._star_direct = _StarDirect(self)
+            self.star_route = "onecall"
+            return d.run(node_lists)
+        if self._ttt_star_direct_ok() and len(node_lists) <= ops.STAR_MAX_STARS and \
+                max(len(nodes) for nodes in node_lists) <= self.nnet.n ** 2 + 1:
+            d = self.__dict__.get("_ttt_star_direct")
+            if d is None:
+                d = self._ttt_star_direct = _TttStarDirect(self)
             self.star_route = "onecall"
             return d.run(node_lists)
         if (not small and self.gnn.num_layers <= ops.STAR_MAX_LAYERS

@@ -12,7 +12,9 @@ MI355X additions (absent from the reference; defaults reproduce its behaviour):
     --parallel_games G       lock-step batched self-play with G concurrent games (selfplay.py)
     --train_parallel MODE    "replicas" | "allreduce" (azhip/dist.py) under torch.distributed
     --gnn_neighbors          the GNN evaluates a leaf with its children as neighbours (MCTS.py);
-                             config key gnn_neighbors, sequential Python search only
+                             config key gnn_neighbors, sequential Python search only; one host
+                             call per leaf (az_c4_star_eval_fwd / az_ttt_star_eval_fwd) on
+                             Connect4 boards with a fused trunk and TicTacToe 3x3 .. 5x5
     --gnn_neighbors_lockstep with --use_gnn --gnn_neighbors: self-play evaluates a round's leaves
                              with their children in ONE batched star call (selfplay.py), so
                              --parallel_games > 1 and several ranks are allowed; config key
@@ -154,7 +156,8 @@ def parse(argv=None):
     p.add_argument("--train_parallel", choices=["replicas", "allreduce"], default=None)
     p.add_argument("--gnn_neighbors", action="store_true", default=None,
                    help="with --use_gnn: the GNN evaluates every leaf together with its children "
-                        "(sequential Python search only)")
+                        "(sequential Python search only); one host call per leaf on Connect4 "
+                        "boards with a fused trunk and on TicTacToe 3x3 .. 5x5")
     p.add_argument("--gnn_neighbors_lockstep", action="store_true", default=None,
                    help="with --use_gnn --gnn_neighbors: lock-step self-play with one batched star "
                         "evaluation per round (allows --parallel_games > 1 and several ranks)")

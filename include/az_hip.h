@@ -771,6 +771,75 @@ size_t az_c4_star_eval_ws_bytes(int max_B, int nx, int ny, int A, int L);
 int az_c4_star_eval_fwd(const az_c4_star_eval* e, const int8_t* boards, const int* counts, int B,
                         float* gpi, float* gv, void* stream);
 
+/* TicTacToe stars: a leaf of an n x n board has up to n^2 children, so a star has up to 10 / 17 /
+ * 26 rows at n = 3 / 4 / 5 -- more than the 9 row slots az_gnn_star_infer is built around. */
+#define AZ_TTT_STAR_MAX_NODES 26   /* a 5x5 leaf and its 25 children */
+/* The layer stack of PolicyValueGNN in eval mode (gnn_utils.py:34-74, 109-112) on B <= 8 PACKED
+ * stars of 1 .. 26 rows: az_gnn_star_infer's arithmetic on az_gnn_star_batch_infer's layout.
+ *   x       [V][F], the packed feature rows of the B stars; never written
+ *   offs    int [B+1], mapped host memory or HBM, ascending, offs[0] = 0, offs[B] = V: star b is
+ *           rows offs[b] .. offs[b+1]-1, its first row the leaf, the rest its neighbours in the
+ *           caller's order
+ *   x0      [B][F]: row 0 of each star after L layers.  May not alias x.
+ * A one-row star passes unchanged bit for bit at every L (gnn_utils.py:35-36), L = 0 is the gather
+ * of the first rows, the weights are divided by their sum only when the sum is > 0
+ * (gnn_utils.py:58-59) and the neighbours are summed in the caller's order.
+ * Four launches per layer, the B row 0s being the rows of one weight-streaming GEMV pass:
+ * attention.0 factored per node, blocks owning 16 hidden units x 256 columns of one star, a wave
+ * taking rows wave, wave + 4, .. (up to 7 per wave); the attention weights and the aggregate per
+ * star (26 H floats of LDS); gate.0 and update_net.0 on [t; agg] as one paired GEMV grid;
+ * update_net.2 with the gated residual t + g * u.  Every output is a fixed-order fp32 fmaf chain,
+ * no atomics, nothing shared between stars: star b's row does not depend on B, on its position in
+ * the pack or on the other stars' sizes, and two calls give equal bits.
+ * 1 <= B <= 8 (B == 0: nothing to do), B <= V <= 26 B, F % 4 == 0, H == AZ_STAR_HIDDEN,
+ * 0 <= L <= 4; x, x0, ws and the weight matrices 16-byte aligned; anything else returns AZ_EINVAL
+ * with a message before any launch; so does an offs in host memory (az_host_alloc / pinned) that
+ * does not ascend from 0 to V in steps of 1 .. 26 -- offs in HBM is clamped into the V rows and
+ * to 26 rows per star by the kernels.  ws >= az_gnn_star_packed_infer_ws_bytes(B, F, H, L)
+ * (0 for a rejected shape). */
+size_t az_gnn_star_packed_infer_ws_bytes(int B, int F, int H, int L);
+int az_gnn_star_packed_infer(const float* x, const int* offs, int B, int V, int F, int H, int L,
+                             const az_gnn_layer_w* layers, float* x0, void* ws, size_t ws_bytes,
+                             void* stream);
+
+/* predict_with_gnn of a TicTacToe leaf with its neighbourhood (TicTacToeGNN.py:47-110 on the star
+ * [board] + neighbor_states: extract_features TicTacToeGNN.py:25-34, PolicyValueGNN.forward
+ * gnn_utils.py:107-116, apply_policy_value_heads TicTacToeGNN.py:36-45 on row 0) as ONE host call
+ * with direct launches: az_ttt_trunk_fwd on the V packed boards, az_gnn_star_packed_infer on the
+ * feature rows, then on the B row 0s the GNN tail of az_ttt_eval_fwd at <= 8 rows
+ * (output_transform.0 + ReLU, output_transform.2, fc1 / fc2 in one launch, az_heads_fwd). */
+typedef struct az_ttt_star_eval {
+  const float* conv1_w; const float* conv1_b; const float* conv2_w; const float* conv2_b;
+  const float* conv3_w; const float* conv3_b;
+  const float* fc1_w; const float* fc1_b;  /* [512][F], [512] */
+  const float* fc2_w; const float* fc2_b;
+  const float* fc_policy_w; const float* fc_policy_b;  /* [A][512], [A] */
+  const float* fc_value_w; const float* fc_value_b;    /* [1][512], [1] */
+  const float* ot0_w; const float* ot0_b;  /* output_transform.0 [F][F], [F] */
+  const float* ot2_w; const float* ot2_b;  /* output_transform.2 */
+  az_gnn_layer_w layers[AZ_STAR_MAX_LAYERS];   /* entries >= L unused */
+  int n;                                   /* board side, 3..5 */
+  int A;                                   /* actions (fc_policy rows), <= 32 */
+  int F;                                   /* 128 (n-2)^2 */
+  int L;                                   /* GNN layers, 0..4 */
+  int max_B;                               /* most stars one call may carry, <= 8 */
+  float* feat;                             /* device [max_B * 26][F] */
+  float* x0; float* hidden; float* y;      /* device [max_B][F] each */
+  float* h1; float* h2;                    /* device [max_B][512] each */
+  float* glogp;                            /* device [max_B][A] */
+  void* ws; size_t ws_bytes;               /* >= az_ttt_star_eval_ws_bytes(max_B, n, A, L) */
+} az_ttt_star_eval;
+/* 0 for a shape az_ttt_star_eval_fwd rejects. */
+size_t az_ttt_star_eval_ws_bytes(int max_B, int n, int A, int L);
+/* rows int8 [V][n][n] packed stars, offs int32 [B+1] (star b = boards offs[b] .. offs[b+1]-1, the
+ * first the leaf; 1 .. 26 boards each), gpi [B][A] (may be NULL), gv [B]; rows, offs, gpi and gv
+ * may be az_host_alloc memory.  0 <= B <= min(max_B, 8) (0: nothing to do), B <= V <= 26 B.  A
+ * star's outputs are bit-identical to the same star evaluated alone or elsewhere in another pack.
+ * A bad shape, a null or misaligned pointer, a small workspace or a bad host offs returns
+ * AZ_EINVAL before any launch. */
+int az_ttt_star_eval_fwd(const az_ttt_star_eval* e, const int8_t* rows, const int* offs, int B,
+                         int V, float* gpi, float* gv, void* stream);
+
 /* Batch-invariant star evaluation (config key batch_invariant with gnn_neighbors).
  *
  * az_gnn_star_batch_exact_infer: az_gnn_star_batch_infer's arguments, offs checks, shape limits
