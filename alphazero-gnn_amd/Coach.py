@@ -3,6 +3,7 @@ libaz_hip networks.  Same episode semantics (temperature schedule, symmetries, G
 'sliding-window' examples from MCTS.expand_tree, reward sign per player), same example
 history, pickle files and checkpoint names, so --load_model resumes from files either
 implementation wrote."""
+import json
 import logging
 import os
 import sys
@@ -252,12 +253,17 @@ class Coach:
             else:
                 pmcts = MCTS(self.game, self.pnet, self.args)
                 pplayer = lambda x: np.argmax(pmcts.getActionProb(x, temp=0))  # noqa: E731
+            log_losses = bool(_flag(self.args, "log_losses"))
+            if log_losses:
+                before = self._evaluate(trainExamples, gnnExamples)
             if use_gnn and gnnExamples:
                 log.info(f"Training with {len(trainExamples)} standard examples and "
                          f"{len(gnnExamples)} GNN examples")
                 self.nnet.train(trainExamples, gnnExamples)
             else:
                 self.nnet.train(trainExamples)
+            if log_losses:
+                self._report_losses(i, before, self._evaluate(trainExamples, gnnExamples))
             if native_arena:
                 nplayer = ArenaPlayer(self.game, self.nnet, self.args)
             else:
@@ -287,6 +293,43 @@ class Coach:
                     self.nnet.save_checkpoint(folder=self.args.checkpoint, filename=it_name)
                     self.nnet.save_checkpoint(folder=self.args.checkpoint, filename=best)
             self._barrier()
+
+    def _evaluate(self, trainExamples, gnnExamples):
+        """args.log_losses: the network's losses on the iteration's examples (nnet.evaluate; every
+        rank computes the whole result, no random number is drawn)."""
+        if _flag(self.args, "use_gnn") and gnnExamples:
+            return self.nnet.evaluate(trainExamples, gnnExamples)
+        return self.nnet.evaluate(trainExamples)
+
+    @staticmethod
+    def _loss_line(m):
+        def part(prefix):
+            return (f"loss {m[prefix + 'loss']:.4f} (pi {m[prefix + 'loss_pi']:.4f}, "
+                    f"v {m[prefix + 'loss_v']:.4f}) top1 {m[prefix + 'top1']:.3f} "
+                    f"n {m[prefix + 'n']}")
+        line = part("")
+        if "gnn_loss" in m:
+            line += f" | gnn {part('gnn_')} | std on gnn examples {part('std_on_gnn_')}"
+        return line
+
+    def _report_losses(self, iteration, before, after):
+        """args.log_losses: two log lines per iteration (the losses on the iteration's examples
+        before and after train()) and the first and last epoch's training loss, plus one JSON line
+        appended to <checkpoint>/losses.jsonl; the writer rank alone logs and writes."""
+        if not self._is_writer():
+            return
+        epochs = list(getattr(self.nnet, "last_train_losses", None) or [])
+        log.info(f"LOSSES iter {iteration} before train: {self._loss_line(before)}")
+        log.info(f"LOSSES iter {iteration} after train:  {self._loss_line(after)}")
+        if epochs:
+            log.info(f"TRAIN LOSS iter {iteration} first epoch: {epochs[0]} ; last epoch: "
+                     f"{epochs[-1]}")
+        folder = self.args.checkpoint
+        if not os.path.exists(folder):
+            os.makedirs(folder)
+        with open(os.path.join(folder, "losses.jsonl"), "a") as f:
+            f.write(json.dumps({"iteration": iteration, "before": before, "after": after,
+                                "train_epochs": epochs}) + "\n")
 
     def saveTrainExamples(self, iteration):
         folder = self.args.checkpoint

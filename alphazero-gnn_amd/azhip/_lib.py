@@ -331,6 +331,9 @@ SIGNATURES = {
                             c_double, c_double, c_int, c_void_p]),
     "az_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double,
                              c_double, c_double, c_int, c_void_p]),
+    "az_policy_value_metrics_ws_bytes": (c_size_t, [c_int, c_int]),
+    "az_policy_value_metrics": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "az_weights_changed": (c_int, []),
     "az_weights_register": (c_int, [c_void_p, c_size_t]),
     "az_weights_unregister": (c_int, [c_void_p]),

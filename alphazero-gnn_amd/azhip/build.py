@@ -33,7 +33,7 @@ SOURCES = ["az_runtime.hip", "az_gemm.hip", "az_gemm_exact.hip", "az_gemm_exact_
            "az_weights.hip", "az_trunk.hip", "az_ttt.hip", "az_c4n.hip", "az_c4r.hip",
            "az_star.hip", "az_star_batch.hip", "az_star_exact.hip", "az_star_train.hip",
            "az_ttt_star.hip", "az_fl.hip", "az_gnn.hip", "az_gnn_fused.hip", "az_gnn_band.hip",
-           "az_optim.hip", "az_backward.hip"]
+           "az_optim.hip", "az_backward.hip", "az_metrics.hip"]
 # No packed-FP32 VALU code (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32): on MI355X a packed op
 # gave wrong low-element results in lanes 48-63 when another workgroup shared the CU (round 6:
 # tools/trunk_selfcheck_probe.py, profiles/r06/trunk_packed_fp32/).  The feature is

@@ -369,6 +369,11 @@ class FrozenLakeNet:
         """FrozenLakeNet.py:76-176: a fresh Adam per call; every epoch shuffles the examples with
         np.random.shuffle and walks them in consecutive batches; a batch with a NaN is skipped."""
         self.nnet.train()
+        # args.log_losses: every epoch's mean batch loss goes into its slot of a device buffer,
+        # read once after the last epoch into last_train_losses (empty when no epoch runs)
+        keep = bool(nets._args_get(self.args, "log_losses", False))
+        if keep:
+            self.last_train_losses = []
         if not examples or len(examples) < 4:
             print("Not enough examples for training, need at least 4")
             return
@@ -377,6 +382,9 @@ class FrozenLakeNet:
         if not examples:
             return
         self.nnet.params.reset_adam()
+        if keep:
+            lbuf = torch.zeros((self.args.epochs,), device=self.device)
+            ran = [False] * self.args.epochs
         for epoch in range(self.args.epochs):
             np.random.shuffle(examples)
             bs = min(len(examples), self.args.batch_size)
@@ -389,9 +397,49 @@ class FrozenLakeNet:
                     continue
                 losses.append(self.train_step(boards, pis, vs))
             if losses:
-                avg = float(torch.cat(losses).mean().item())
+                mean = torch.cat(losses).mean()
+                if keep:
+                    lbuf[epoch].copy_(mean)
+                    ran[epoch] = True
+                avg = float(mean.item())
                 print(f"Epoch {epoch + 1}/{self.args.epochs} - Loss: {avg:.4f}")
         torch.cuda.current_stream(self.device).synchronize()
+        if keep:
+            host = lbuf.cpu().numpy()
+            self.last_train_losses = [dict(epoch=e, **({"loss": float(host[e])} if ran[e] else {}))
+                                      for e in range(self.args.epochs)]
+
+    def evaluate(self, examples, chunk=4096):
+        """The losses of the network on `examples` ((board, pi, v), as train() takes them; v None
+        is dropped as there) without training on them -> {loss_pi, loss_v, loss, top1, entropy,
+        target_entropy, n} (NetWrapper.evaluate's keys; loss_pi + loss_v is the loss train()
+        minimises).  Every board is evaluated on the leaf train() builds for it (_nodes_of) by
+        az_fl_eval_fwd, `chunk` leaves a call, and scored by az_policy_value_metrics straight from
+        the mapped host memory the evaluator wrote; one device-to-host read at the end.  Draws no
+        random number, writes no weight or optimiser state and leaves the training flag as it
+        was."""
+        from . import metrics
+        chunk = max(1, int(chunk))
+        examples = [(x[0], x[1], x[2]) for x in (examples or []) if x[2] is not None]
+        mode = self.nnet.training
+        sums = metrics.MetricSums(self.device, 1)
+        try:
+            if examples:
+                tpi, tv = metrics._targets([e[1] for e in examples], [e[2] for e in examples],
+                                           ACTIONS, self.device)
+                for c0 in range(0, len(examples), chunk):
+                    part = examples[c0:c0 + chunk]
+                    pend = self._launch_nodes([self._nodes_of(np.asarray(e[0], dtype=np.float32))
+                                               for e in part])
+                    sums.hold.append(pend)
+                    st = pend.staging
+                    sums.add(0, st.pi[:len(part)], st.v[:len(part)], tpi[c0:c0 + chunk],
+                             tv[c0:c0 + chunk])
+            host = sums.read()
+        finally:
+            sums.hold.clear()
+            self.nnet.train(mode)
+        return ops.metrics_dict(host[0])
 
     # -- checkpoints -------------------------------------------------------------------------
     def save_checkpoint(self, folder, filename):

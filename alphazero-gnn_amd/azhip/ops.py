@@ -1220,6 +1220,52 @@ def adam(p, g, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-8):
                              _stream()), "az_adam_step")
 
 
+# ----------------------------------------------------------------------------- metrics
+METRICS = ("ce", "se", "top1", "entropy", "target_entropy", "n")   # AZ_METRICS_* order
+
+
+def policy_value_metrics(p, v, target_pi, target_v, acc=None, accumulate=False, is_log=False,
+                         ws=None):
+    """az_policy_value_metrics: the sums of METRICS over the B rows of p [B][A] (probabilities, or
+    log-probabilities with is_log; rows may be strided), v [B] against target_pi [B][A] and
+    target_v [B] -> acc, a float64 [6] device tensor (made when None; added to with accumulate).
+    Inputs are device tensors or HostBuffer views.  Nothing here waits for the device."""
+    B, A = p.shape
+    for t, name in ((p, "p"), (v, "v"), (target_pi, "target_pi"), (target_v, "target_v")):
+        _need(t, name=name)
+    if tuple(target_pi.shape) != (B, A) or v.numel() != B or target_v.numel() != B:
+        raise ValueError(f"policy_value_metrics: shapes p {tuple(p.shape)} v {tuple(v.shape)} "
+                         f"target_pi {tuple(target_pi.shape)} target_v {tuple(target_v.shape)}")
+    if B and (p.stride(1) != 1 or not target_pi.is_contiguous() or not v.is_contiguous()
+              or not target_v.is_contiguous()):
+        raise ValueError("policy_value_metrics: p needs unit column stride, the rest contiguous")
+    if acc is None:
+        if accumulate:
+            raise ValueError("policy_value_metrics: accumulate needs acc")
+        acc = torch.empty((len(METRICS),), dtype=torch.float64, device=_dev(target_pi))
+    _need(acc, torch.float64, "acc")
+    L = _lib.lib()
+    nb = int(L.az_policy_value_metrics_ws_bytes(B, A))
+    if ws is None or ws.numel() < nb:
+        ws = torch.empty((max(nb, 8),), dtype=torch.uint8, device=acc.device)
+    _lib.check(L.az_policy_value_metrics(_p(p), p.stride(0) if B > 1 else max(A, 1), int(is_log),
+                                         _p(v), _p(target_pi), _p(target_v), B, A, _p(acc),
+                                         int(accumulate), _p(ws), _stream()),
+               "az_policy_value_metrics")
+    return acc
+
+
+def metrics_dict(sums, prefix=""):
+    """Host sums in METRICS order -> the dict evaluate() reports: means over the rows (loss_pi,
+    loss_v, loss = their sum, top1, entropy, target_entropy) and n; zeros for no rows."""
+    s = [float(x) for x in sums]
+    n = int(round(s[5]))
+    d = max(n, 1)
+    out = {"loss_pi": s[0] / d, "loss_v": s[1] / d, "loss": (s[0] + s[1]) / d, "top1": s[2] / d,
+           "entropy": s[3] / d, "target_entropy": s[4] / d, "n": n}
+    return {prefix + k: x for k, x in out.items()}
+
+
 # ----------------------------------------------------------------------------- backward
 def heads_loss_bwd(logp, v, target_pi, target_v, B_norm=None, loss_rows=None):
     B, A = logp.shape

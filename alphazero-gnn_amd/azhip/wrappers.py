@@ -1187,6 +1187,14 @@ class NetWrapper:
         with replacement by np.random.randint; GNN step on a second sample)."""
         lr = self.args.lr
         self._sync_params()
+        # args.log_losses: the (l_pi, l_v) every step already forms on the device go into one slot
+        # per epoch and are read once after the last epoch (no per-epoch host read); without the
+        # key nothing is allocated and the launches are the ones of a run without it
+        keep = bool(nets._args_get(self.args, "log_losses", False))
+        if keep:
+            lbuf = torch.zeros((self.args.epochs, 4), device=self.device)
+            cnn_ran, gnn_ran = [False] * self.args.epochs, [False] * self.args.epochs
+        cnn_split = False
         if (nets._args_get(self.args, "train_parallel", "replicas") == "auto"
                 and getattr(self, "_tp_auto", None) is None):
             from . import dist as D
@@ -1196,34 +1204,78 @@ class NetWrapper:
         self.nnet.params.reset_adam()
         if self.has_gnn:
             self.gnn.params.reset_adam()
-        for _ in range(self.args.epochs):
+        for epoch in range(self.args.epochs):
             self.nnet.train()
             if self.has_gnn:
                 self.gnn.train()
+            loss = gloss = None
             if examples:
                 b, p, v = self._cnn_batch(examples)
                 self.train_seed += 1
                 if self._dp_world() > 1:
-                    self._cnn_step_allreduce(b, p, v, lr)
+                    # the rows are split over the ranks: this is this rank's rows' part of the
+                    # loss (normalised by the global batch); the parts are summed once, below
+                    loss = self._cnn_step_allreduce(b, p, v, lr)
+                    cnn_split = True
+                    if keep:
+                        cnn_ran[epoch] = True     # a rank without rows adds nothing to the sum
                 else:
-                    T.cnn_step(self.nnet, b, p, v, lr, seed=self.train_seed)
+                    loss = T.cnn_step(self.nnet, b, p, v, lr, seed=self.train_seed)
             if (self.has_gnn and gnn_examples and len(gnn_examples) > 0
                     and nets._args_get(self.args, "gnn_neighbors_train", False)):
                 # every example on its own child star; deterministic, so it runs whole on every
                 # rank in every train_parallel mode and the replicas stay equal
                 rows, offs, p, v = self._gnn_star_batch(gnn_examples)
                 self.train_seed += 1
-                T.gnn_star_step(self.nnet, self.gnn, rows, offs, p, v, lr, seed=self.train_seed)
+                gloss = T.gnn_star_step(self.nnet, self.gnn, rows, offs, p, v, lr,
+                                        seed=self.train_seed)
             elif self.has_gnn and gnn_examples and len(gnn_examples) > 0:
                 b, p, v = self._gnn_batch(gnn_examples)
                 self.train_seed += 1
                 if self._dp_world() > 1:
-                    T.gnn_step_dp(self.nnet, self.gnn, b, p, v, lr, seed=self.train_seed,
-                                  grad_sync=nets._args_get(self.args, "gnn_grad_sync", "row0"))
+                    gloss = T.gnn_step_dp(self.nnet, self.gnn, b, p, v, lr, seed=self.train_seed,
+                                          grad_sync=nets._args_get(self.args, "gnn_grad_sync",
+                                                                   "row0"))
                 else:
-                    T.gnn_step(self.nnet, self.gnn, b, p, v, lr, seed=self.train_seed)
+                    gloss = T.gnn_step(self.nnet, self.gnn, b, p, v, lr, seed=self.train_seed)
+            if keep and loss is not None:
+                lbuf[epoch, 0:2].copy_(loss)
+                cnn_ran[epoch] = True
+            if keep and gloss is not None:
+                lbuf[epoch, 2:4].copy_(gloss)
+                gnn_ran[epoch] = True
+        if keep and cnn_split:
+            # train_parallel = "allreduce": one all_reduce of every epoch's CNN loss parts, queued
+            # behind the last step (only under the key; the steps' own collectives are untouched)
+            from . import dist as D
+            parts = lbuf[:, 0:2].contiguous()
+            D.allreduce_sum_(parts)
+            lbuf[:, 0:2].copy_(parts)
         torch.cuda.current_stream().synchronize()
+        if keep:
+            from . import metrics
+            self.last_train_losses = metrics.train_losses(lbuf, cnn_ran, gnn_ran)
 
+    def evaluate(self, examples, gnn_examples=None, chunk=4096):
+        """The losses of the network on `examples` ((board, pi, v) tuples, as train() takes
+        them) without training on them -> {loss_pi, loss_v, loss, top1, entropy, target_entropy,
+        n}: loss_pi = mean -sum(pi log p), loss_v = mean (v - z)^2, loss their sum (the quantity
+        train() minimises), top1 the share of rows whose argmax p is argmax pi, the two entropies
+        in nats, n the row count; all zeros for no examples.  On a GNN wrapper `gnn_examples`
+        (Coach's seven fields; board, expanded_pi and expanded_v are read) add gnn_* -- the GNN
+        outputs against expanded_pi / expanded_v -- and std_on_gnn_* -- the standard heads on the
+        same boards against the same targets, from the same forward -- so that their difference
+        is what the GNN buys.  The outputs are the search's: eval mode, the per-board route of
+        predict_both on a batch (the exact one under args.batch_invariant); under
+        args.gnn_neighbors the gnn_examples' boards are scored with their child stars
+        (stars.board_stars, predict_both_stars), the standard block's boards -- whose outputs
+        no star changes -- stay on the per-board route.  `chunk` boards are evaluated at a time
+        and scored by az_policy_value_metrics into accumulators on the device, read once at the
+        end (azhip/metrics.py).  Draws no random number, writes no parameter, optimiser state or
+        train_seed, leaves the training flags as they were; under a process group every rank
+        computes the whole result."""
+        from . import metrics
+        return metrics.evaluate_wrapper(self, examples, gnn_examples, chunk)
 
     def _dp_world(self):
         """>1 when the train steps are data-parallel over ranks (args.train_parallel ==
@@ -1331,12 +1383,14 @@ class NetWrapper:
             mask = ops.dropout_mask(Bg * F, drop, self.train_seed, self.device)[r0 * F:r1 * F]
         P = self.nnet.params
         if r1 > r0:
-            T.cnn_grads(self.nnet, b[r0:r1], p[r0:r1], v[r0:r1], seed=self.train_seed,
-                        drop_mask=mask, B_norm=Bg)
+            loss = T.cnn_grads(self.nnet, b[r0:r1], p[r0:r1], v[r0:r1], seed=self.train_seed,
+                               drop_mask=mask, B_norm=Bg)
         else:
             P.grad_flat.zero_()
+            loss = None
         D.allreduce_sum_(P.grad_flat)
         T.adam_step(self.nnet, lr)
+        return loss
 
     def snapshot(self):
         """Device copy of every parameter buffer (Coach's temp checkpoint, in memory)."""

@@ -30,6 +30,14 @@ MI355X additions (absent from the reference; defaults reproduce its behaviour):
                              the default routes.  With --gnn_neighbors (with or without
                              --gnn_neighbors_lockstep) the stars take az_star_eval_exact_fwd, for
                              --gnn_layers up to 4; config key batch_invariant
+    --log_losses             report losses: every iteration evaluates the network on the
+                             iteration's examples before and after train() (nnet.evaluate: policy
+                             and value loss, top-1 agreement, entropies; with --use_gnn also the
+                             GNN outputs and the standard heads against the expand_tree targets),
+                             logs both with the first and last epoch's training loss
+                             (nnet.last_train_losses) and appends one JSON line to
+                             <checkpoint>/losses.jsonl; examples, shuffles, arena and checkpoints
+                             are the same bits with or without it; config key log_losses
     multi-GPU: python -m torch.distributed.run --nproc-per-node P --master-addr 127.0.0.1 main.py ...
                (one rank per GPU, backend nccl = RCCL; episodes sharded by index)
 """
@@ -168,6 +176,9 @@ def parse(argv=None):
                    help="evaluate every board with the same bits at any batch size (exact-fp32 "
                         "GEMMs; slower; with --gnn_neighbors also the star evaluation, "
                         "--gnn_layers up to 4)")
+    p.add_argument("--log_losses", action="store_true", default=None,
+                   help="evaluate the network on every iteration's examples before and after "
+                        "train(), log the losses and append them to <checkpoint>/losses.jsonl")
     return p.parse_args(argv)
 
 
@@ -188,7 +199,7 @@ def build_args(a):
     args = config_to_args(config)
     for k in ("board_size", "board_rows", "numIters", "numMCTSSims", "parallel_games",
               "train_parallel", "gnn_neighbors", "gnn_neighbors_lockstep", "gnn_neighbors_train",
-              "batch_invariant"):
+              "batch_invariant", "log_losses"):
         if getattr(a, k) is not None:
             args[k] = getattr(a, k)
     args.use_gnn = a.use_gnn

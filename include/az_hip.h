@@ -999,6 +999,39 @@ int az_adam_f32(float* p, const float* g, float* m, float* v, int64_t n,
 int az_adam_step(float* p, const float* g, float* m, float* v, int64_t n,
                  double lr, double beta1, double beta2, double eps, int step, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Loss metrics of B rows of network outputs against their targets, summed over the rows into
+ * acc[AZ_METRICS_N] (doubles on the device; a mean is acc[k] / acc[AZ_METRICS_ROWS]):
+ *   AZ_METRICS_CE    -sum_a t log p     policy cross-entropy (train()'s l_pi times B)
+ *   AZ_METRICS_SE    (tv - v)^2         value squared error  (train()'s l_v times B)
+ *   AZ_METRICS_TOP1  argmax p == argmax t, ties to the lowest index on both sides
+ *   AZ_METRICS_ENT   -sum_a p log p     policy entropy
+ *   AZ_METRICS_TENT  -sum_a t log t     target entropy
+ *   AZ_METRICS_ROWS  B
+ * p [B][ldp] (ldp >= A) holds probabilities (is_log = 0) or log-probabilities (is_log = 1); v,
+ * target_v [B]; target_pi [B][A]; 1 <= A <= 32.  A term with t == 0 is exactly 0 whatever p is;
+ * log p is never taken below log(FLT_MIN), so p == 0 under t > 0 adds the finite -t log(FLT_MIN),
+ * and p == 0 adds 0 to the entropy: no NaN or inf from zeros.  The per-row terms are formed in
+ * fp32 and summed over the rows in fp64 in a fixed order without atomics (per-block sums into ws,
+ * then one block adds them in block order), so two identical calls give equal bits.
+ * accumulate != 0 adds the sums to what acc holds, so a chunked pass needs one device-to-host read
+ * at its end and no host synchronisation; otherwise acc is overwritten.  B == 0 is valid: acc is
+ * left as it is when accumulating and zeroed otherwise.  ws >= az_policy_value_metrics_ws_bytes(B,
+ * A) bytes, 8-byte aligned (may be NULL when B == 0).  A bad shape, a null pointer or a
+ * misaligned acc / ws returns AZ_EINVAL before any launch.
+ * --------------------------------------------------------------------------------- */
+#define AZ_METRICS_CE 0
+#define AZ_METRICS_SE 1
+#define AZ_METRICS_TOP1 2
+#define AZ_METRICS_ENT 3
+#define AZ_METRICS_TENT 4
+#define AZ_METRICS_ROWS 5
+#define AZ_METRICS_N 6
+size_t az_policy_value_metrics_ws_bytes(int B, int A);
+int az_policy_value_metrics(const float* p, int ldp, int is_log, const float* v,
+                            const float* target_pi, const float* target_v, int B, int A,
+                            double* acc, int accumulate, void* ws, void* stream);
+
 /* Parameters changed: every cached per-row weight scale and fp16 weight plane of the fp16 GEMM
  * form (az_gemm_f32's large K-major GEMMs on registered weights, below) is recomputed before its
  * next use.  The cache is keyed by the weight pointer and shape, so a caller that writes
