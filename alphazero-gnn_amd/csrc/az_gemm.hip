@@ -2433,10 +2433,30 @@ static void launch_cfg(Tile cfg, const GemmArgs& a, bool akm, bool bkm, hipStrea
   }
 }
 
+// AZ_GEMM_PRINT (tuning build): one stderr line per gemm_f32_partial call naming the launch --
+// "gemm M= N= K=: <family> ..." with MR / S for the GEMVs, splits / kc for the tiles and vec_epi --
+// and one per splitk_reduce call ("reduce4<S>" or "scalar"): tests/test_gpu_gemm_dispatch.py
+// reads them to hold its shape table to the dispatch.  Nothing in the product build.
+#ifdef AZ_TUNING
+static bool gemm_print_on() {
+  static const bool v = tuning_env("AZ_GEMM_PRINT") != nullptr;
+  return v;
+}
+#define AZ_GEMM_PRINT(a, fmt, ...)                                                              \
+  do {                                                                                          \
+    if (gemm_print_on())                                                                        \
+      fprintf(stderr, "gemm M=%d N=%d K=%d: " fmt " vec_epi=%d\n", (a).M, (a).N, (a).K,         \
+              __VA_ARGS__, (a).vec_epi);                                                        \
+  } while (0)
+#else
+#define AZ_GEMM_PRINT(a, fmt, ...) do {} while (0)
+#endif
+
 template <int MR, int S, int R>
 static bool try_gemv_full(const GemmArgs& a, hipStream_t s) {
   if constexpr (MR * S <= 32) {
     if (a.K > 256 * S) return false;
+    AZ_GEMM_PRINT(a, "gemv_full MR=%d S=%d", MR, S);
     const int nblk = (a.N + 4 * R - 1) / (4 * R);
     hipLaunchKernelGGL((gemv_full<MR, S, R>), dim3(nblk), dim3(256), 0, s, a);
     return true;
@@ -2457,6 +2477,7 @@ static void launch_gemv(const GemmArgs& a, hipStream_t s) {
   static const bool chunked = tuning_env("AZ_GEMV_CHUNKED") != nullptr;   // A/B experiments
   if (!chunked && a.M >= 3 && a.K > 256 * 8 && a.K <= 256 * 13) {
     // 2 rows per LDS group, 2 weight rows per wave
+    AZ_GEMM_PRINT(a, "gemv_rows MR=%d S=%d", 2, 13);
     hipLaunchKernelGGL((gemv_rows<13, 2, 2>), dim3((a.N + 7) / 8), dim3(256), 0, s, a);
     return;
   }
@@ -2471,6 +2492,7 @@ static void launch_gemv(const GemmArgs& a, hipStream_t s) {
     if (done) return;
   }
   const int nblk = (a.N + 4 * GV_ROWS - 1) / (4 * GV_ROWS);
+  AZ_GEMM_PRINT(a, "gemv_f32 MR=%d S=%d", a.M <= 2 ? a.M : a.M <= 4 ? 4 : 8, 0);
   switch (a.M) {
     case 1: hipLaunchKernelGGL(gemv_f32<1>, dim3(nblk), dim3(256), 0, s, a); break;
     case 2: hipLaunchKernelGGL(gemv_f32<2>, dim3(nblk), dim3(256), 0, s, a); break;
@@ -3192,7 +3214,10 @@ int gemm_f32_partial(const az_gemm_desc* d, hipStream_t s, int* splits_out, cons
     launch_gemv(a, s);
     return check_launch("gemv_f32");
   }
-  if (akm && bkm && launch_tall(a, s)) return check_launch("gemm_tall");
+  if (akm && bkm && launch_tall(a, s)) {
+    AZ_GEMM_PRINT(a, "tall splits=%d kc=%d", 1, a.K);
+    return check_launch("gemm_tall");
+  }
   const bool glds_ok = akm && bkm && !d->A2 && !d->a_rows;
   // the heads from the tiles (az_x3.h HeadsEpi): only a plain y = x W^T + b, whole 32-column
   // chunks, A <= 8; launch_x3 takes it on its P2 split-K tiles and says so in a.heads_done
@@ -3202,6 +3227,7 @@ int gemm_f32_partial(const az_gemm_desc* d, hipStream_t s, int* splits_out, cons
   if (glds_ok && d->M > 8 && d->K >= 1024 && d->N >= 256 && launch_x3(a, d->ws_bytes, s, pre)) {
     *splits_out = a.splits;
     if (heads_done) *heads_done = a.heads_done != 0;
+    AZ_GEMM_PRINT(a, "x3 splits=%d kc=%d", a.splits, a.kc);
     return check_launch("gemm_x3");
   }
   a.he = HeadsEpi{};
@@ -3214,7 +3240,13 @@ int gemm_f32_partial(const az_gemm_desc* d, hipStream_t s, int* splits_out, cons
     cfg = TILE_GLDS2_256x128;
   } else if (glds_ok && d->N >= 1024 && d->K >= 1024 && full_waves_256x128(d->M, d->N)) {
     // large M whose 256x128 grid is (nearly) whole rounds of 256 blocks: the 8-wave tile's
-    // steady state wins (M = 65,536: 130 vs 109 TFLOP/s for 128x64)
+    // steady state wins (M = 65,536: 130 vs 109 TFLOP/s for 128x64).
+    // For M > 64 this is the tuning build's branch (AZ_GEMM_X3=0): launch_x3 above has taken every
+    // K-major shape with M > 64, K >= 1024, N >= 256.  The product rules get here only with
+    // 9 <= M <= 64 (launch_x3 declines) and >= 973 column tiles, N >= 124,417 -- no network
+    // here has such a layer, and the tile is then one 256-row block of <= 64 live rows with
+    // plan()'s split (AZ_GEMM_PRINT: rule=full_waves; tests/test_gpu_gemm_dispatch.py runs one).
+    // Otherwise the product build reaches this tile through splits_256x128 alone.
     cfg = TILE_GLDS2_256x128;
   } else if (glds_ok && d->M > 128) {
     // LDS-DMA tiles: 128x64 once the grid fills the chip, 128x128 + split-K below that
@@ -3241,6 +3273,12 @@ int gemm_f32_partial(const az_gemm_desc* d, hipStream_t s, int* splits_out, cons
     a.kc = S > 1 ? ((a.K + S - 1) / S + 31) / 32 * 32 : a.K;
     if (S > 1) a.splits = (a.K + a.kc - 1) / a.kc;
   }
+#ifdef AZ_TUNING
+  static const char* const kNames[] = {"reg64", "glds128x128", "glds128x64", "glds2_256x128",
+                                       "ring_256x128", "ring_st_256x128"};
+  AZ_GEMM_PRINT(a, "%s splits=%d kc=%d rule=%s", kNames[cfg], a.splits, a.kc,
+                cfg < TILE_GLDS2_256x128 ? "tile" : s256 > 0 ? "splits_256x128" : "full_waves");
+#endif
   launch_cfg(cfg, a, akm, bkm, s);
   *splits_out = a.splits;
   return check_launch("gemm_f32_mfma");
@@ -3263,6 +3301,14 @@ int splitk_reduce(const az_gemm_desc* d, int splits, hipStream_t s) {
                    (!d->R || (d->ldr % 4 == 0 && aligned16(d->R))) &&
                    (!d->G || (d->ldg % 4 == 0 && aligned16(d->G))) &&
                    (!d->bias || aligned16(d->bias)) && aligned16(d->ws);
+#ifdef AZ_TUNING
+  if (gemm_print_on()) {
+    if (vec && splits >= 2 && splits <= 8)
+      fprintf(stderr, "reduce M=%d N=%d: reduce4<%d>\n", a.M, a.N, splits);
+    else
+      fprintf(stderr, "reduce M=%d N=%d: scalar splits=%d\n", a.M, a.N, splits);
+  }
+#endif
   if (vec && splits >= 2 && splits <= 8) {
     // float4 per lane: 38.7 MB at M = 512, N = 3136, S = 5 in one pass (the scalar
     // grid-stride kernel took 10.6 us for it)
